@@ -8,7 +8,7 @@ AdamW).  Inputs are synthetic and resident in HBM: chains start from the target'
 network from the flax-style initialiser; the warm-up (default 201 iterations: one full cycle and the MALA + training half of the
 next) trains it so the timed flow steps integrate a non-trivial field.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 K should be a multiple of the 101-iteration cycle (default 1010 = ten cycles: 10 flow steps + 1000 MALA iterations, the mix the
@@ -273,6 +273,31 @@ def usable_cores():
     return max(1, n)
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: ``arrays`` (name -> host array) as ``out_dir/<name>.npy``, float32 arrays as float32 and everything else as
+    float64.  Should they exceed ``limit`` bytes in all, the largest is replaced by a sample of its elements (flattened, at indices
+    drawn from a fixed seed, in ascending order: the same indices on every run with the same arguments) that fits in what is left."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    sampled = []
+    while sum(v.nbytes for v in out.values()) > limit:
+        k = max(out, key=lambda n: out[n].nbytes)
+        room = (limit - sum(v.nbytes for n, v in out.items() if n != k)) // out[k].itemsize
+        if room < 1 or k in sampled:
+            raise ValueError(f"--dump-outputs: the outputs do not fit in {limit} bytes")
+        flat = out[k].reshape(-1)
+        out[k] = flat[np.sort(np.random.default_rng(0).choice(flat.size, size=room, replace=False))]
+        sampled.append(k)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    print(f"bench.py: outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {list(v.shape)}{' (sample)' if k in sampled else ''}"
+                                                                         for k, v in out.items()), file=sys.stderr)
+
+
 def pmc_traffic(kernel_class, workload="phi-four"):
     """HBM bytes per launch of the dominant kernel from the committed rocprofv3 PMC summary (separate --pmc passes of this
     same command, tools/prof_round.sh): 2 * FETCH_SIZE + WRITE_SIZE, both reported in KB; the factor 2 is the gfx950
@@ -304,14 +329,14 @@ def pmc_traffic(kernel_class, workload="phi-four"):
     return None, None
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=1010)      # ten full (K+1)-cycles: a flow step lasts as long as its SLOWEST chain (an
-                                                             # extreme statistic of 4096 adaptive solves: 510..620 attempted steps from
-                                                             # one flow step to the next), so two cycles are a noisy sample of it
-    ap.add_argument("--warmup", type=int, default=201)      # one full cycle (incl. its flow step: first launch, scratch set-up) + the
-                                                             # MALA iterations of the next: the timed region then holds two complete
+    ap.add_argument("--steps", type=int, default=None)      # default 1010, ten full (K+1)-cycles: a flow step lasts as long as its SLOWEST
+                                                             # chain (an extreme statistic of 4096 adaptive solves: 510..620 attempted
+                                                             # steps from one flow step to the next), so two cycles are a noisy sample of it
+    ap.add_argument("--warmup", type=int, default=None)     # default 201, one full cycle (incl. its flow step: first launch, scratch set-up)
+                                                             # + the MALA iterations of the next: the timed region then holds complete
                                                              # cycles, each STARTING with its flow step (whose tail produces the draws
                                                              # of the 100 iterations after it, noise.hip: produced and used inside)
     ap.add_argument("--chains-per-gpu", type=int, default=0)
@@ -320,8 +345,23 @@ def main():
                          "gaussian-mixture / 4-mode: the d = 2 mixtures of configs[1] / configs[0] (exact trace + eval_step every iteration)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fixed-step", action="store_true", help="skip the fixed-step (RK4 / Euler) flow-step report that follows the timed region")
-    a = ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (chain states, acceptance, loss, network parameters) "
+                         "as DIR/<name>.npy, float32 / float64, at most 64 MB in all; with more than one rank, rank 0's chains")
+    a = ap.parse_args(argv)
+    if a.steps is None and a.warmup is None and a.workload in ("pines", "4-mode"):
+        # pines: two cycles after two cycles of training (the timed flow steps integrate a field that has trained for 200+ iterations);
+        # 4-mode (K = 10): twenty 11-iteration cycles after two.  Explicit --steps / --warmup are always taken as given.
+        a.steps, a.warmup = {"pines": (202, 202), "4-mode": (220, 22)}[a.workload]
+    a.steps = 1010 if a.steps is None else a.steps
+    a.warmup = 201 if a.warmup is None else a.warmup
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
 
+
+def main():
+    a = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -362,10 +402,6 @@ def main():
     wl_example, wl_dim, wl_h, _, wl_chains, wl_K = WORKLOADS[a.workload]
     if not a.chains_per_gpu:
         a.chains_per_gpu = wl_chains
-    if a.workload == "pines" and a.steps == 1010 and a.warmup == 201:     # two cycles after two cycles of training: the timed flow
-        a.steps, a.warmup = 202, 202                                       # steps integrate a field that has trained for 200+ iterations
-    if a.workload == "4-mode" and a.steps == 1010 and a.warmup == 201:    # K = 10: twenty 11-iteration cycles after two
-        a.steps, a.warmup = 220, 22
     n_total = a.chains_per_gpu * world            # weak scaling: per-GPU work fixed
     args = make_args(n_total, learning_iter=10000, workload=a.workload)
     d2 = a.workload in D2
@@ -472,6 +508,12 @@ def main():
     # after an (uninstrumented) flow step whose tail has produced their draws; without it a timed region that ends with its
     # cycle leaves these iterations drawing in line (mala_step 38 us instead of 10, the training kernel 65 instead of 43)
     ctx.profile(False)
+    if a.dump_outputs and rank == 0:                         # before the passes below move the chains and the network on
+        v = eng.n_valid
+        outputs = {"positions": pos[:v].cpu().numpy(), "logdensity": logp[:v].cpu().numpy(), "logdensity_grad": grad[:v].cpu().numpy(),
+                   "acceptance": acc[:v].cpu().numpy(), "loss": eng.loss.cpu().numpy(), "params": ctx.get_params()}
+        if d2:
+            outputs["eval_loss"] = eval_out.cpu().numpy()
     natt_timed, nflow_timed = natt_sum.clone(), n_flow[0]    # the tallies of the timed region: the flow step below is not part of it
     count += (wl_K + 1) - count % (wl_K + 1)
     step(total, count)
@@ -603,6 +645,8 @@ def main():
                     out["cpu_baseline"].update(extra)
             except Exception as e:  # the baseline must never hide the GPU number
                 out["cpu_baseline"] = {"value": None, "unit": "chain-steps/s", "cores": 0, "kind": "port", "sample": f"failed: {e!r}"}
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if td is not None:
         td.barrier()

@@ -1,6 +1,6 @@
 /* libmfm_hip -- C ABI of the MI355X-native Markovian Flow Matching inner loop.
  *
- * This is the drop-in boundary for the hot path of albcab/mfm (reference paths relative to /root/reference):
+ * This is the drop-in boundary for the hot path of albcab/mfm (reference paths relative to the root of that repository):
  * every entry point replaces one jit-compiled XLA executable (or a piece of one) that the reference's `run()` loop
  * (exe_flow_matching.py:432-449) calls.  The reference has no FFI of its own (it is pure Python on JAX); the
  * binding a maintainer adds is the ctypes layer in mfm_amd/_lib.py.

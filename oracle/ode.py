@@ -2,7 +2,7 @@
 
 ORACLE (test infrastructure; see oracle/__init__.py).  ``odeint`` is a third-party
 dependency of the reference (jax 0.4.26, ``environment.yaml:101``; call site
-``exe_flow_matching.py:13,345-349``) that is absent from ``/root/reference``; this is a
+``exe_flow_matching.py:13,345-349``) that is not part of the reference repository; this is a
 restatement of its published algorithm (PARITY UNPINNED; pinned against closed-form
 linear flows and scipy RK45 in tests/test_oracle_ode.py):
 
