@@ -104,7 +104,10 @@ __device__ __forceinline__ float adam_update(float w, float g, float& m, float& 
   v = __builtin_fmaf(b2, v, (1.f - b2) * g * g);
   float u = (m / bc1) / (sqrtf(v / bc2) + eps);
   if (decay) u = __builtin_fmaf(wd, w, u);
-  u = fminf(fmaxf(-lr * u, -clip), clip);
+  // optax.clip (jnp.clip) propagates a NaN update -- the 11th non-finite gradient in a row is applied and leaves NaN parameters.
+  // fminf / fmaxf return the non-NaN operand: alone they would turn that update into -clip and the run into finite garbage.
+  u = -lr * u;
+  u = __builtin_isnan(u) ? u : fminf(fmaxf(u, -clip), clip);
   return w + u;
 }
 

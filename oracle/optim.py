@@ -5,7 +5,7 @@ ORACLE (test infrastructure; see oracle/__init__.py).  Follows
 ``flax.training.train_state.TrainState.apply_gradients`` (``:366``).  The update
 rules are the published ones of optax 0.1.9 (``environment.yaml:177``): PARITY
 UNPINNED against optax itself; pinned against ``torch.optim.AdamW`` (same rule) in
-tests/test_oracle_optim.py.  Quirks kept: ``optax.clip`` clips the
+tests/test_oracle_optim_ode_mala.py.  Quirks kept: ``optax.clip`` clips the
 final UPDATES elementwise; the schedule is ``lr * (1 - count / learning_iter)``
 evaluated at the inner optimizer's pre-increment count.
 """

@@ -32,17 +32,26 @@ def target_block(dist):
     raise NotImplementedError(dist.kind)
 
 
-def make_ctx(dist, args, n_local=None, n_total=None, offset=0, fourier=None, params=None, max_eval=0, family=None):
+OPT_KEYS = ("learning_rate", "adam_b1", "adam_b2", "adam_eps", "weight_decay", "update_clip", "learning_iter", "warmup_steps")
+
+
+def make_ctx(dist, args, n_local=None, n_total=None, offset=0, fourier=None, params=None, max_eval=0, family=None, opt=None):
+    """``opt``: optimizer settings (keys OPT_KEYS) that replace the ones taken from ``args``.  They reach the optimizer only: the
+    vector field's gradient clip stays ``args.gradient_clip`` (d > 128) whatever ``opt["update_clip"]`` is."""
     from mfm_amd import _lib
     n_local = args.num_chain if n_local is None else n_local
+    opt = dict(opt or {})
+    assert set(opt) <= set(OPT_KEYS), sorted(set(opt) - set(OPT_KEYS))
+    hyper = dict(learning_rate=args.learning_rate, adam_b1=args.adam_beta1, adam_b2=args.adam_beta2, adam_eps=args.adam_epsilon,
+                 weight_decay=args.weight_decay, update_clip=args.gradient_clip, learning_iter=args.learning_iter,
+                 warmup_steps=args.warmup_steps)
+    hyper.update(opt)
     ctx = _lib.Context(
         dim=args.dim, fourier_dim=args.fourier_dim, hidden_t=args.hidden_t, hidden_x=args.hidden_x,
         hidden_xt=args.hidden_xt, n_chain_local=n_local, n_chain_total=n_total or n_local, chain_offset=offset,
         grad_clip=(args.gradient_clip if args.dim > 128 else 0.0), sigma=args.sigma, cond_flow=int(args.cond_flow),
         hutch=int(args.hutchs), rtol=args.rtol, atol=args.atol, mxstep=int(args.mxstep), n_ts=args.n_ts,
-        learning_rate=args.learning_rate, adam_b1=args.adam_beta1, adam_b2=args.adam_beta2, adam_eps=args.adam_epsilon,
-        weight_decay=args.weight_decay, update_clip=args.gradient_clip, learning_iter=args.learning_iter,
-        warmup_steps=args.warmup_steps, max_eval_samples=max_eval, activation=_lib.ACTIVATIONS[args.non_linearity],
+        **hyper, max_eval_samples=max_eval, activation=_lib.ACTIVATIONS[args.non_linearity],
         ref_std=float(np.sqrt(targets.REF_VARS[getattr(args, "ref_dist", "stdgauss")])),
         ode_method=_lib.ODE_METHODS[getattr(args, "ode_method", "dopri5")] if int(getattr(args, "ode_steps", 0) or 0) > 0 else 0,
         ode_steps=int(getattr(args, "ode_steps", 0) or 0),

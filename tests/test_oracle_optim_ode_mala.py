@@ -9,26 +9,69 @@ from oracle import flow, mala, ode, optim, prng, targets
 
 
 def test_adamw_chain_matches_torch():
+    """Large decay (0.3) on the kernels, none on the biases, warmup + linear decay set per step: the oracle follows torch's AdamW
+    to rounding.  torch decays first, p (1 - lr wd) - lr adam; optax adds wd p to the update, p - lr (adam + wd p): the same
+    expression, so the two differ by float32 rounding only, whatever wd."""
     rng = np.random.default_rng(0)
     params = [{"kernel": rng.standard_normal((5, 4)).astype(np.float32), "bias": rng.standard_normal(4).astype(np.float32)}]
-    n_steps, lr0 = 7, 1e-2
-    st = optim.TrainState(params, optim.learning_rate_fn(n_steps, 0, lr0))
+    n_steps, warmup, lr0, wd = 9, 3, 1e-2, 0.3
+    lr_fn = optim.learning_rate_fn(n_steps, warmup, lr0)
+    st = optim.TrainState(params, lr_fn, weight_decay=wd)
     W = torch.tensor(params[0]["kernel"].copy(), requires_grad=True)
     b = torch.tensor(params[0]["bias"].copy(), requires_grad=True)
-    opt = torch.optim.AdamW([{"params": [W], "weight_decay": 1e-4}, {"params": [b], "weight_decay": 0.0}],
+    opt = torch.optim.AdamW([{"params": [W], "weight_decay": wd}, {"params": [b], "weight_decay": 0.0}],
                             lr=lr0, betas=(0.9, 0.999), eps=1e-8)
-    for s in range(n_steps):
+    decayed = 0.0
+    for s in range(n_steps + 2):                 # through the warmup, the decay and two steps at lr 0
         g = {"kernel": rng.standard_normal((5, 4)).astype(np.float32), "bias": rng.standard_normal(4).astype(np.float32)}
-        lr = lr0 * (1 - s / n_steps)
+        lr = lr_fn(s)
         for grp in opt.param_groups:
             grp["lr"] = lr
         W.grad, b.grad = torch.tensor(g["kernel"]), torch.tensor(g["bias"])
         opt.step()
         assert st.apply_gradients([g])
-        # torch decays with p *= 1 - lr*wd BEFORE the adam term; optax adds wd*p to the update: equal to O(lr^2 wd)
+        decayed += lr * wd
         np.testing.assert_allclose(st.params[0]["kernel"], W.detach().numpy(), rtol=2e-6, atol=2e-7)
         np.testing.assert_allclose(st.params[0]["bias"], b.detach().numpy(), rtol=2e-6, atol=2e-7)
-    assert st.step == n_steps and st.count == n_steps
+    assert decayed > 1e-2                        # the decay moved the kernels by ~1e-2 |w|: far above the tolerance
+    assert st.step == n_steps + 2 and st.count == n_steps + 2
+
+
+def _optax_linear_schedule(init_value, end_value, transition_steps):
+    """optax.linear_schedule (polynomial_schedule, power 1, transition_begin 0), restated in float64."""
+    if transition_steps <= 0:
+        return lambda count: init_value
+    def schedule(count):
+        count = min(max(count, 0), transition_steps)
+        frac = 1 - count / transition_steps
+        return (init_value - end_value) * frac + end_value
+    return schedule
+
+
+def _optax_join_schedules(schedules, boundaries):
+    def schedule(step):
+        output = schedules[0](step)
+        for boundary, sched in zip(boundaries, schedules[1:]):
+            output = output if step < boundary else sched(step - boundary)
+        return output
+    return schedule
+
+
+@pytest.mark.parametrize("warmup", [0, 1, 3])
+def test_learning_rate_fn_matches_optax_join_schedules(warmup):
+    """exe_flow_matching.py:189-198 -- join_schedules([linear(0 -> lr, warmup), linear(lr -> 0, n - warmup)], [warmup]) -- against
+    the oracle's schedule and the host's create_learning_rate_fn, at both ends of both branches and beyond."""
+    from mfm_amd import exe_flow_matching as E
+    n, lr0 = 9, 1e-2
+    ref = _optax_join_schedules([_optax_linear_schedule(0.0, lr0, warmup), _optax_linear_schedule(lr0, 0, n - warmup)], [warmup])
+    o, h = optim.learning_rate_fn(n, warmup, lr0), E.create_learning_rate_fn(n, warmup, lr0)
+    steps = sorted({0, max(warmup - 1, 0), warmup, warmup + 1, n - 1, n, n + 1, n + 7})
+    for s in steps:
+        assert o(s) == ref(s), (warmup, s, o(s), ref(s))
+        assert abs(h(s) - o(s)) <= 1e-15 * lr0, (warmup, s, h(s), o(s))
+    assert o(0) == (0.0 if warmup else lr0) and o(warmup) == lr0 and o(n) == 0.0 and o(n + 7) == 0.0
+    if warmup > 1:
+        assert abs(o(1) - lr0 / warmup) <= 1e-15 * lr0
 
 
 def test_apply_if_finite_and_clip():
