@@ -79,9 +79,13 @@ typedef struct mfm_config {
   /* BUILD-SIDE MODE, not in the reference (whose integrator is the adaptive Dopri5 of jax.experimental.ode.odeint,
      exe_flow_matching.py:345-349 -- ode_method = MFM_ODE_DOPRI5, the default): the CNF solves on ode_steps EQUAL steps of classical
      RK4 (MFM_ODE_RK4) or forward Euler (MFM_ODE_EULER), the "RK4/Euler ODE integrator" BASELINE.json's north star names -- no step-size
-     controller, every chain takes the same steps.  Built for the shape-specialised solver (default widths, PhiFour, relu, hutch = 1,
-     random-walk flow step and the transforms); other configurations fail with MFM_EUNSUPPORTED at the first solve.  rtol / atol /
-     mxstep are ignored in this mode; n_ts > 2 needs ode_steps % (n_ts - 1) == 0. */
+     controller, every chain takes the same steps.  Served by the shape-specialised solver (default widths, PhiFour, relu, hutch = 1:
+     random-walk flow step and the transforms), the wide family (every other network depth or width, LGCP, the exact-trace solves of
+     fused-family contexts at d >= 16: both flow-step modes and the transforms) and the d = 2 four-chain tiles (the mixtures without
+     --hutch: both flow-step modes and the transforms).  Still MFM_EUNSUPPORTED at the first solve: the generic 16-chain tile (d = 2
+     with hutch = 1, MFM_D2_TILE=16, MFM_TILE_EXACT=1, and the fused family's other shapes), the independent flow step on the
+     shape-specialised tile, and mfm_debug_replay.  rtol / atol / mxstep are ignored in this mode; n_ts > 2 needs
+     ode_steps % (n_ts - 1) == 0.  mfm_get_counters: field_evals = 4 (RK4) or 1 (Euler) x attempted steps. */
   int32_t ode_method, ode_steps;
 } mfm_config;
 

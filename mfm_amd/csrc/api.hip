@@ -1038,7 +1038,9 @@ extern "C" int mfm_get_counters(mfm_ctx* x, int64_t h_out[8]) { use_ctx(x);
   HIPCHK(hipMemcpy(&att, x->d_att, sizeof att, hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; ++i) h_out[i] = x->ctr[i];
   h_out[CTR_ATTEMPTS] = (int64_t)att;
-  h_out[CTR_FIELD_EVALS] = 2 * x->ctr[CTR_SOLVES] + 6 * (int64_t)att;      // odeint: f(y0), the initial-step probe, six stages per attempt
+  if (x->cfg.ode_method != MFM_ODE_DOPRI5 && x->cfg.ode_steps > 0)          // fixed steps: four (RK4) or one (Euler) evaluation per step
+    h_out[CTR_FIELD_EVALS] = (x->cfg.ode_method == MFM_ODE_RK4 ? 4 : 1) * (int64_t)att;
+  else h_out[CTR_FIELD_EVALS] = 2 * x->ctr[CTR_SOLVES] + 6 * (int64_t)att;      // odeint: f(y0), the initial-step probe, six stages per attempt
   return MFM_OK;
 }
 extern "C" int mfm_reset_counters(mfm_ctx* x) { use_ctx(x);
@@ -1085,18 +1087,19 @@ extern "C" int mfm_ode_transform(mfm_ctx* x, int direction, int per_chain, const
   a.in = d_in; a.out = d_out; a.ldj = d_ldj; a.n = n;
   a.nsteps = d_nsteps = att_buffer(x, d_nsteps, n);
   a.rp = x->replay; a.rp.n = n; memset(&x->replay, 0, sizeof x->replay);      // one-shot
-  if ((x->wide || x->wide_ex) && a.fixed_steps > 0) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): built for the shape-specialised solver");
   if (wide::Ctx* ws = x->wide ? x->wide : x->wide_ex) {
+    if (a.fixed_steps > 0 && a.rp.dt) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): the prescribed-step replay (mfm_debug_replay) is for the adaptive solver");
     launch_probe(per_chain ? 0 : 1, d_keys, a.key, 0, 0, 0, n, x->net.d, const_cast<float*>(a.z1), x->stream);
     wide::WReplay wr{a.rp.dt, a.rp.acc, a.rp.ratio, a.rp.dt_own, a.rp.cap, a.rp.n, 0, 0, nullptr};
-    const int rcw = wide::transform(ws, x->net, direction, a.rtol, a.atol, a.max_attempts, a.z1, d_in, n, d_out, d_ldj, d_nsteps, x->stream, wr);
+    const int rcw = wide::transform(ws, x->net, direction, a.rtol, a.atol, a.max_attempts, a.z1, d_in, n, d_out, d_ldj, d_nsteps, x->stream, wr,
+                                    a.fixed_method, a.fixed_steps);
     if (rcw) return fail(rcw, "wide ODE transform failed: %s", hipGetErrorString(hipGetLastError()));
     LAUNCHCHK();
     tally_solves(x, d_nsteps, n, 1);
     return MFM_OK;
   }
   int rc = launch_ode_transform(a, x->stream);
-  if (rc == -4) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): built for the shape-specialised solver -- default widths, PhiFour, relu, hutch");
+  if (rc == -4) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): not built for the generic 16-chain tile (d = 2 with --hutch, MFM_D2_TILE=16, MFM_TILE_EXACT) nor for the prescribed-step replay");
   if (rc) return fail(rc, "ODE kernel cannot be launched for this configuration");
   LAUNCHCHK();
   tally_solves(x, d_nsteps, n, 1);
@@ -1138,21 +1141,21 @@ extern "C" int mfm_flow_step(mfm_ctx* x, int mode, uint32_t k0, uint32_t k1, dou
   int rc = 0;
   {
     ProfScope ps_(x, PROF_FLOW);
-    if ((x->wide || x->wide_ex) && a.fixed_steps > 0) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): built for the shape-specialised solver");
     if (wide::Ctx* ws = x->wide ? x->wide : x->wide_ex) {
+      if (a.fixed_steps > 0 && a.rp.dt) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): the prescribed-step replay (mfm_debug_replay) is for the adaptive solver");
       launch_probe(2, nullptr, f.key, f.n_total, f.chain_offset, 0, a.n, x->net.d, const_cast<float*>(a.zgen), x->stream);     // key_gen
       launch_probe(2, nullptr, f.key, f.n_total, f.chain_offset, 3, a.n, x->net.d, const_cast<float*>(a.z1), x->stream);       // key_hutch2
       launch_probe(2, nullptr, f.key, f.n_total, f.chain_offset, 2, a.n, x->net.d, const_cast<float*>(a.z2), x->stream);       // key_hutch1
       wide::FlowCall c; memset(&c, 0, sizeof c);
       c.mode = mode; c.key = f.key; c.n_total = f.n_total; c.chain_offset = f.chain_offset; c.beta = beta; c.rows = a.n; c.ref_std = f.ref_std;
-      c.rtol = a.rtol; c.atol = a.atol; c.max_attempts = a.max_attempts; c.z_inv = a.z1; c.z_fwd = a.z2; c.zgen = a.zgen;
+      c.rtol = a.rtol; c.atol = a.atol; c.max_attempts = a.max_attempts; c.fixed_method = a.fixed_method; c.fixed_steps = a.fixed_steps; c.z_inv = a.z1; c.z_fwd = a.z2; c.zgen = a.zgen;
       c.pos = d_pos; c.logp = d_logp; c.grad = d_grad; c.acc_prob = d_acc; c.accepted = d_isacc; c.proposed = d_prop; c.nsteps = d_nsteps;
       c.rp = wide::WReplay{a.rp.dt, a.rp.acc, a.rp.ratio, a.rp.dt_own, a.rp.cap, a.rp.n, 0, 0, a.rp.diag};
       const int rcw = wide::flow_step(ws, x->net, c, x->stream);
       if (rcw) return fail(rcw, "wide flow step failed: %s", hipGetErrorString(hipGetLastError()));
     } else {
       rc = launch_flow_step(a, f, nz, x->stream);
-      if (rc == -4) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): built for the shape-specialised solver -- default widths, PhiFour, relu, hutch, random-walk flow step");
+      if (rc == -4) return fail(MFM_EUNSUPPORTED, "fixed-step mode (ode_method / ode_steps): not built for the generic 16-chain tile (d = 2 with --hutch, MFM_D2_TILE=16, MFM_TILE_EXACT), the independent flow step of the shape-specialised tile, nor the prescribed-step replay");
       if (rc) return fail(rc, "flow step cannot be launched for this configuration");
     }
     LAUNCHCHK();

@@ -1290,7 +1290,9 @@ int launch_ode_transform(const OdeArgs& a, hipStream_t stream) {
   if (ode_check(a.net, sm, tpw)) return -3;
   if (a.hutch) launch_probe(a.per_chain_keys ? 0 : 1, a.keys, a.key, 0, 0, 0, a.n, a.net.d, const_cast<float*>(a.z1), stream);
   if (a.fixed_steps > 0) {
-    if (!fast::shape_ok(a.net, a.hutch) || a.rp.dt) return -4;
+    if (a.rp.dt) return -4;
+    if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_fixed(a, nullptr, stream);
+    if (!fast::shape_ok(a.net, a.hutch)) return -4;
     return fast::launch_transform_fixed(a, a.fixed_method, a.fixed_steps, a.fast_scr, stream);
   }
   if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_transform(a, stream);
@@ -1314,7 +1316,9 @@ int launch_flow_step(const OdeArgs& a, const FlowArgs& f, const NoiseArgs& nz, h
     launch_probe(2, nullptr, f.key, f.n_total, f.chain_offset, 2, a.n, a.net.d, const_cast<float*>(a.z2), stream);     // key_hutch1
   }
   if (a.fixed_steps > 0) {
-    if (!fast::shape_ok(a.net, a.hutch) || a.rp.dt || (f.mode & 0xFF) != MFM_FLOW_RWMH) return -4;
+    if (a.rp.dt) return -4;
+    if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_fixed(a, &f, stream);
+    if (!fast::shape_ok(a.net, a.hutch) || (f.mode & 0xFF) != MFM_FLOW_RWMH) return -4;
     return fast::launch_flow_fixed(a, f, a.fixed_method, a.fixed_steps, a.fast_scr, stream);
   }
   if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_flow(a, f, stream);

@@ -650,7 +650,52 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
   natt = (int)na;
 }
 
-template <typename TILE>
+// Fixed-step mode (mfm_config.ode_method / ode_steps; the shape-specialised tile's ode_fixed.hip restated for the 4-chain tiles): N
+// equal steps of classical RK4 or forward Euler, chain g's state redundant in every lane of group g as in solve(), the same stage
+// evaluation, no controller.  The time batch is the one of an attempt: prepare() takes five stage times -- two RK4 steps (t, t + h/2,
+// t + h, t + 3h/2, t + 2h) or five Euler steps -- and eval() reads slot s at phase 2 + s (phases 2 .. 6: the streamed tile
+// re-evaluates its time branch in each, as it reuses it at phase 7 only).  Oracle: oracle/ode.py: odeint_fixed.
+enum { FIX_RK4 = 1, FIX_EULER = 2 };      // = MFM_ODE_RK4 / MFM_ODE_EULER
+template <int METHOD, typename TILE>
+__device__ __forceinline__ void solve_fixed(TILE& T, int nsteps, float (&y)[2], float& ell) {
+  constexpr int SPB = METHOD == FIX_RK4 ? 2 : 5;       // steps per time batch
+  const float h = 1.f / (float)nsteps;
+  float el = 0.f;
+#pragma unroll 1
+  for (int n0 = 0; n0 < nsteps; n0 += SPB) {
+    float ts5[5];
+#pragma unroll
+    for (int s = 0; s < 5; ++s) ts5[s] = METHOD == FIX_RK4 ? ((float)(2 * n0 + s) * 0.5f) * h : (float)(n0 + s) * h;
+    T.prepare(ts5);
+#pragma unroll 1
+    for (int ss = 0; ss < SPB && n0 + ss < nsteps; ++ss) {
+      float kv[2], dl;
+      if constexpr (METHOD == FIX_EULER) {
+        T.eval(y[0], y[1], ts5[ss], kv, dl, 2 + ss);
+        y[0] = fmaf(h, kv[0], y[0]); y[1] = fmaf(h, kv[1], y[1]);
+        el = fmaf(h, dl, el);
+      } else {
+        float k[4][2], l[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // stage j at slot 2 ss + {0, 1, 1, 2}, input y + {0, h/2 k1, h/2 k2, h k3}
+          const int sl = 2 * ss + (j == 0 ? 0 : (j == 3 ? 2 : 1));
+          const float a = j == 0 ? 0.f : (j == 3 ? h : 0.5f * h);
+          const float x0 = j == 0 ? y[0] : fmaf(a, k[j - 1][0], y[0]), x1 = j == 0 ? y[1] : fmaf(a, k[j - 1][1], y[1]);
+          T.eval(x0, x1, ts5[sl], kv, dl, 2 + sl);
+          k[j][0] = kv[0]; k[j][1] = kv[1]; l[j] = dl;
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) y[q] = fmaf(h / 6.f, (k[0][q] + k[3][q]) + 2.f * (k[1][q] + k[2][q]), y[q]);
+        el = fmaf(h / 6.f, (l[0] + l[3]) + 2.f * (l[1] + l[2]), el);
+      }
+    }
+  }
+  ell = el;
+}
+
+// METHOD 0: the adaptive solve (the kernels of the adaptive path); FIX_RK4 / FIX_EULER: a.fixed_steps equal steps
+template <typename TILE, int METHOD = 0>
 __global__ __launch_bounds__(NW * 64) void transform_kernel(OdeArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   TILE T;
@@ -658,7 +703,8 @@ __global__ __launch_bounds__(NW * 64) void transform_kernel(OdeArgs a) {
   T.sign = a.direction;
   const int b = T.chain();
   float y[2] = {a.in[(size_t)b * 2], a.in[(size_t)b * 2 + 1]}, ell; int natt;
-  solve(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, 0, b);
+  if constexpr (METHOD == 0) solve(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, 0, b);
+  else { solve_fixed<METHOD>(T, a.fixed_steps, y, ell); natt = a.fixed_steps; }
   if (T.writer()) {
     a.out[(size_t)b * 2] = y[0]; a.out[(size_t)b * 2 + 1] = y[1];
     a.ldj[b] = ell;
@@ -667,7 +713,7 @@ __global__ __launch_bounds__(NW * 64) void transform_kernel(OdeArgs a) {
 }
 
 // One flow-based MH step per chain (random-walk in latent space :264-278, or independent :246-260).
-template <typename TILE>
+template <typename TILE, int METHOD = 0>
 __global__ __launch_bounds__(NW * 64) void flow_kernel(OdeArgs a, FlowArgs f) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
 #ifdef MFM_STAMPS
@@ -698,7 +744,8 @@ __global__ __launch_bounds__(NW * 64) void flow_kernel(OdeArgs a, FlowArgs f) {
       if (f.mode == MFM_FLOW_IMH) lq_ref = -0.5f * (r0 - r1) / (f.ref_std * f.ref_std);             // :254-255
     }
     T.sign = ph == 0 ? -1 : 1;
-    solve(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, ph, b);
+    if constexpr (METHOD == 0) solve(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, ph, b);
+    else { solve_fixed<METHOD>(T, a.fixed_steps, y, ell); natt = a.fixed_steps; }
     natt_tot += natt;
   }
   // ---- target at the proposal (:270 / :252), tempered: beta * loglik + logprior (the mixture has no prior term) ----
@@ -746,16 +793,16 @@ static int pick(const NetDev& n, int hutch, int rows) {       // 0: generic 16-c
   return (e || rows / 16 < 256) ? 1 : 0;
 }
 static bool use_for(const NetDev& n, int hutch, int rows) { return pick(n, hutch, rows) != 0; }
-template <typename TILE>
+template <typename TILE, int METHOD = 0>
 static int launch_transform_t(const OdeArgs& a, size_t sm, hipStream_t stream) {
-  (void)hipFuncSetAttribute((const void*)transform_kernel<TILE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(transform_kernel<TILE>, dim3(a.n / TILE::CHAINS), dim3(NW * 64), sm, stream, a);
+  (void)hipFuncSetAttribute((const void*)transform_kernel<TILE, METHOD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+  hipLaunchKernelGGL((transform_kernel<TILE, METHOD>), dim3(a.n / TILE::CHAINS), dim3(NW * 64), sm, stream, a);
   return 0;
 }
-template <typename TILE>
+template <typename TILE, int METHOD = 0>
 static int launch_flow_t(const OdeArgs& a, const FlowArgs& f, size_t sm, hipStream_t stream) {
-  (void)hipFuncSetAttribute((const void*)flow_kernel<TILE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-  hipLaunchKernelGGL(flow_kernel<TILE>, dim3(a.n / TILE::CHAINS), dim3(NW * 64), sm, stream, a, f);
+  (void)hipFuncSetAttribute((const void*)flow_kernel<TILE, METHOD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+  hipLaunchKernelGGL((flow_kernel<TILE, METHOD>), dim3(a.n / TILE::CHAINS), dim3(NW * 64), sm, stream, a, f);
   return 0;
 }
 static int launch_transform(const OdeArgs& a, hipStream_t stream) {
@@ -773,6 +820,23 @@ static int launch_flow(const OdeArgs& a, const FlowArgs& f, hipStream_t stream) 
   }
 
   return launch_flow_t<Tile>(a, f, (size_t)layout(a.net).total * sizeof(float), stream);
+}
+// fixed-step mode on the tiling pick() names (callers check pick() != 0)
+template <int METHOD>
+static int launch_fixed_m(const OdeArgs& a, const FlowArgs* f, hipStream_t stream) {
+  if (pick(a.net, a.hutch, a.n) == 2) {
+    const size_t sm = (size_t)layout_r().total * sizeof(float);
+    if (a.net.act == MFM_ACT_RELU)
+      return f ? launch_flow_t<TileR<MFM_ACT_RELU>, METHOD>(a, *f, sm, stream) : launch_transform_t<TileR<MFM_ACT_RELU>, METHOD>(a, sm, stream);
+    return f ? launch_flow_t<TileR<-1>, METHOD>(a, *f, sm, stream) : launch_transform_t<TileR<-1>, METHOD>(a, sm, stream);
+  }
+  const size_t sm = (size_t)layout(a.net).total * sizeof(float);
+  return f ? launch_flow_t<Tile, METHOD>(a, *f, sm, stream) : launch_transform_t<Tile, METHOD>(a, sm, stream);
+}
+static int launch_fixed(const OdeArgs& a, const FlowArgs* f, hipStream_t stream) {
+  if (a.fixed_method == FIX_RK4) return launch_fixed_m<FIX_RK4>(a, f, stream);
+  if (a.fixed_method == FIX_EULER) return launch_fixed_m<FIX_EULER>(a, f, stream);
+  return -4;
 }
 
 }  // namespace d2

@@ -9,7 +9,8 @@
 //   Euler : one batch serves FIVE steps, five evaluations.
 // Oracle: oracle/ode.py: odeint_fixed (float64, checked against closed forms, scipy and the oracle's own Dopri5); parity:
 // tests/test_gpu_fixed.py.  mfm_config.ode_method / ode_steps select it (include/mfm.h); the Hutchinson log-det, the flow-MH
-// acceptance (exe_flow_matching.py:264-278) and every draw are those of the adaptive path.
+// acceptance (exe_flow_matching.py:264-278) and every draw are those of the adaptive path.  The same mode on the wide family and the
+// d = 2 four-chain tiles: wide.hip / ode_d2.hip: solve_fixed.
 namespace fast {
 
 enum { ODE_RK4 = 1, ODE_EULER = 2 };

@@ -1737,6 +1737,153 @@ static int solve(Ctx* w, const NetDev& n, const SolveArgs& c, float* xstage, hip
   return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- fixed-step mode (mfm_config.ode_method / ode_steps): N equal steps of classical RK4 or forward Euler ----------------
+// The host-driven restatement of ode_fixed.hip for the wide family: every row takes every step, so a solve is a launch sequence
+// known when it starts -- no controller, no row compaction, no read-back.  Per stage: fixed_input_kernel (stage input), the
+// field evaluation of the adaptive solve (field_eval: Hutchinson integrand or exact trace), fixed_finish_kernel (stage
+// derivative, divergence term; at the step's last stage the step combination).  The time branch is batched as in the adaptive
+// loop: one GEMM chain on 5 rows-row slots serves two RK4 steps (t, t + h/2, t + h, t + 3h/2, t + 2h) or five Euler steps.
+// Oracle: oracle/ode.py: odeint_fixed.
+enum { FIX_RK4 = 1, FIX_EULER = 2 };      // = MFM_ODE_RK4 / MFM_ODE_EULER
+struct FixBuf {
+  int rows, d, dp, F, F2p, sign, method;
+  float h;
+  float* Y;            // [rows][dp] state
+  float* K;            // [4][rows][dp] stage derivatives (RK4; Euler uses none)
+  float* X;            // [rows][dp] stage input
+  float *kl, *ell;     // [4][rows] divergence terms of the step's stages, [rows] log-det
+  const float* Z;      // probe (Hutchinson) or null
+  const float* trp;    // exact trace partial sums or null
+  float* ffat5;        // [5][rows][F2p] Fourier rows of the batch's stage times
+  const float* fourier;
+  const float* out; const float* outT; const float* gate; const float* gc; const float* hz;
+};
+struct FixTimes { float t[5]; int n; };   // stage times of a time batch (n slots; n = 0: none written)
+
+// stage input X = Y + coef K_src (coef = 0: X = Y); with tb.n > 0 also the Fourier rows of the batch's stage times (:70-71, :229)
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_input_kernel(FixBuf a, int src, float coef, FixTimes tb) {
+  using V = RowV<T>;
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.rows) return;
+  const size_t o0 = (size_t)b * a.dp, ks = (size_t)a.rows * a.dp;
+  for (int col = lane * V::W; col < a.dp; col += 64 * V::W) {
+    T v = V::zero();
+    if (col < a.d) {
+      v = V::ld(a.Y + o0 + col);
+      if (coef != 0.f) v += coef * V::ld(a.K + src * ks + o0 + col);
+    }
+    V::st(a.X + o0 + col, v);
+  }
+#pragma unroll 1
+  for (int sl = 0; sl < tb.n; ++sl) {
+    const double te = a.sign > 0 ? (double)tb.t[sl] : 1.0 - (double)tb.t[sl];
+    fourier_row(a.fourier, a.F, a.F2p, te, a.ffat5 + ((size_t)sl * a.rows + b) * a.F2p, lane);
+  }
+}
+
+// end of stage j's evaluation: k_j = +-v, kl_j = -+ div (as stage_finish_kernel); at the step's last stage (`last`) the step
+// combination Y += h/6 (k1 + 2 k2 + 2 k3 + k4), ell += h/6 (...) (RK4) or Y += h k1, ell += h kl1 (Euler).  Each wavefront reads back
+// only the K columns its own lanes wrote.
+template <typename T>
+__global__ __launch_bounds__(256) void fixed_finish_kernel(FixBuf a, int j, int last) {
+  using V = RowV<T>;
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.rows) return;
+  const size_t o0 = (size_t)b * a.dp, ks = (size_t)a.rows * a.dp;
+  const bool rk4 = a.method == FIX_RK4;
+  const float h = a.h, h6 = a.h / 6.f;
+  float dpart = 0.f;
+  for (int col = lane * V::W; col < a.d; col += 64 * V::W) {
+    const size_t o = o0 + col;
+    const T gt = V::ld(a.gate + o);
+    T v = V::ld(a.out + o) + gt * V::ld(a.gc + o);
+    if (a.sign < 0) v = -v;
+    if (a.Z) dpart += V::sum(V::ld(a.Z + o) * (V::ld(a.outT + o) + gt * V::ld(a.hz + o)));
+    else if (a.trp) dpart += V::sum(gt * V::ld(a.hz + o));
+    if (!rk4) V::st(a.Y + o, V::ld(a.Y + o) + h * v);
+    else if (!last) V::st(a.K + j * ks + o, v);
+    else {
+      const T s = (V::ld(a.K + o) + v) + 2.f * (V::ld(a.K + ks + o) + V::ld(a.K + 2 * ks + o));
+      V::st(a.Y + o, V::ld(a.Y + o) + h6 * s);
+    }
+  }
+  dpart = wave_sum(dpart);
+  if (a.trp) {
+#pragma unroll
+    for (int sl = 0; sl < JT_SLICES; ++sl) dpart += a.trp[(size_t)b * JT_SLICES + sl];
+  }
+  const float dl = a.sign > 0 ? -dpart : dpart;                 // :218 / :239
+  if (lane == 0) {
+    const int R = a.rows;
+    if (!rk4) a.ell[b] += h * dl;
+    else if (!last) a.kl[j * R + b] = dl;
+    else a.ell[b] += h6 * ((a.kl[b] + dl) + 2.f * (a.kl[R + b] + a.kl[2 * R + b]));
+  }
+}
+
+__global__ void fixed_init_kernel(float* ell, int* natt, int rows, int nsteps) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b < rows) { ell[b] = 0.f; natt[b] = nsteps; }
+}
+
+struct FixedArgs { int sign, method, nsteps, rows; };
+
+// Integrate rows of w->Y (padded [rows][dp]) from t = 0 to 1 on c.nsteps equal steps with the probe in w->zp; results as solve():
+// w->Y, w->rs.ell, w->rs.natt (= nsteps).  Launches only: no synchronisation, no device-to-host copy.
+static int solve_fixed(Ctx* w, const NetDev& n, const FixedArgs& c, float* xstage, hipStream_t s) {
+  const int rows = c.rows, N = c.nsteps;
+  if (N < 1 || (c.method != FIX_RK4 && c.method != FIX_EULER)) return -3;
+  const bool exact = w->exact, rk4 = c.method == FIX_RK4;
+  const int fmode = exact ? 2 : 1;
+  if (exact) {
+    if (!w->master || jt_alloc(w, n)) return -4;
+    jt_setup(w, n, s);
+  }
+  FixBuf a; memset(&a, 0, sizeof a);
+  a.rows = rows; a.d = n.d; a.dp = n.dp; a.F = n.F; a.F2p = n.F2p; a.sign = c.sign; a.method = c.method; a.h = 1.f / (float)N;
+  a.Y = w->Y; a.K = w->K; a.X = xstage; a.kl = w->rs.kl; a.ell = w->rs.ell;
+  a.Z = exact ? nullptr : w->zp; a.trp = exact ? w->jtP : nullptr; a.ffat5 = w->ffat5; a.fourier = n.fourier;
+  a.out = w->out; a.outT = w->outT; a.gc = w->gc; a.hz = w->hz;
+  hipLaunchKernelGGL(fixed_init_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, w->rs.ell, w->rs.natt, rows, N);
+  if (!exact) probe_setup(w, n, rows, s);
+  const bool vec4 = (n.d & 3) == 0 && (n.dp & 3) == 0;
+  const float h = a.h;
+  const int spb = rk4 ? 2 : 5;           // steps per time batch
+  float* const cat_keep = w->catv;
+  for (int n0 = 0; n0 < N; n0 += spb) {
+    const int steps = N - n0 < spb ? N - n0 : spb;
+    FixTimes tb;
+    tb.n = rk4 ? 2 * steps + 1 : steps;  // a partial last batch evaluates the time branch of the slots it uses only
+    for (int sl = 0; sl < 5; ++sl) tb.t[sl] = rk4 ? ((float)(2 * n0 + sl) * 0.5f) * h : (float)(n0 + sl) * h;
+    bool first = true;
+    for (int ss = 0; ss < steps; ++ss) {
+      const int nst = rk4 ? 4 : 1;
+      for (int j = 0; j < nst; ++j) {
+        const int slot = rk4 ? 2 * ss + (j == 0 ? 0 : (j == 3 ? 2 : 1)) : ss;
+        const float coef = j == 0 ? 0.f : (j == 3 ? h : 0.5f * h);
+        FixTimes t0 = tb;
+        if (!first) t0.n = 0;
+        if (vec4) hipLaunchKernelGGL(fixed_input_kernel<f32x4>, dim3(grid4(rows)), dim3(256), 0, s, a, j - 1, coef, t0);
+        else hipLaunchKernelGGL(fixed_input_kernel<float>, dim3(grid4(rows)), dim3(256), 0, s, a, j - 1, coef, t0);
+        if (first) {
+          time_branch_on(w, n, w->ffat5, w->ta5, w->cat5, w->gate5, false, tb.n * rows, s);
+          first = false;
+        }
+        FixBuf ab = a;
+        ab.gate = w->gate5 + (size_t)slot * rows * n.dp;
+        w->catv = w->cat5 + (size_t)slot * rows * w->cat;        // x2 writes its sx half into the slot's [sx | st] rows, j1 reads them
+        field_eval(w, n, xstage, fmode, false, rows, s);
+        w->catv = cat_keep;
+        const int last = j + 1 == nst ? 1 : 0;
+        if (vec4) hipLaunchKernelGGL(fixed_finish_kernel<f32x4>, dim3(grid4(rows)), dim3(256), 0, s, ab, j, last);
+        else hipLaunchKernelGGL(fixed_finish_kernel<float>, dim3(grid4(rows)), dim3(256), 0, s, ab, j, last);
+      }
+    }
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 
 static void pad_rows(const float* src, int n, int d, int dp, float* dst, hipStream_t s) {
   hipLaunchKernelGGL(pad_rows_kernel, dim3(grid_el((size_t)n * dp)), dim3(256), 0, s, src, n, d, dp, dst);
@@ -1746,15 +1893,16 @@ static void unpad_rows(const float* src, int n, int d, int dp, float* dst, hipSt
 }
 
 // transform_and_logdet / inverse_and_logdet (:206-242) on n samples, R rows per pass.  z: Hutchinson probes [n][d].
+// fixed_steps > 0: fixed-step mode (solve_fixed, method fixed_method; rtol / atol / max_attempts unused)
 static int transform(Ctx* w, const NetDev& n, int direction, float rtol, float atol, int max_attempts, const float* z, const float* in,
-                     int cnt, float* out, float* ldj, int* nsteps, hipStream_t s, WReplay rp = WReplay{}) {
+                     int cnt, float* out, float* ldj, int* nsteps, hipStream_t s, WReplay rp = WReplay{}, int fixed_method = 0, int fixed_steps = 0) {
   for (int r0 = 0; r0 < cnt; r0 += w->R) {
     const int rows = cnt - r0 < w->R ? cnt - r0 : w->R;
     pad_rows(in + (size_t)r0 * n.d, rows, n.d, n.dp, w->Y, s);
     pad_rows(z + (size_t)r0 * n.d, rows, n.d, n.dp, w->zp, s);
     rp.solve = 0; rp.row0 = r0;
     SolveArgs c{direction, rtol, atol, max_attempts, rows, rp};
-    const int rc = solve(w, n, c, w->cond, s);
+    const int rc = fixed_steps > 0 ? solve_fixed(w, n, FixedArgs{direction, fixed_method, fixed_steps, rows}, w->cond, s) : solve(w, n, c, w->cond, s);
     if (rc) return rc;
     unpad_rows(w->Y, rows, n.d, n.dp, out + (size_t)r0 * n.d, s);
     if (hipMemcpyAsync(ldj + r0, w->rs.ell, rows * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return -4;
@@ -1766,6 +1914,7 @@ static int transform(Ctx* w, const NetDev& n, int direction, float rtol, float a
 struct FlowCall {
   int mode; Key2 key; uint32_t n_total, chain_offset; double beta; int rows; float ref_std;
   float rtol, atol; int max_attempts;
+  int fixed_method, fixed_steps;              // fixed_steps > 0: both solves on fixed steps (solve_fixed)
   const float *z_inv, *z_fwd, *zgen;          // [rows][d]: key_hutch2, key_hutch1, key_gen draws (:265 / :247)
   float* pos; double* logp; float* grad; float* acc_prob; uint8_t* accepted; float* proposed; int* nsteps;
   WReplay rp;
@@ -1784,13 +1933,14 @@ static int flow_step(Ctx* w, const NetDev& n, const FlowCall& c, hipStream_t s) 
   SolveArgs sa{-1, c.rtol, c.atol, c.max_attempts, rows, c.rp};
   sa.rp.solve = 0; sa.rp.row0 = 0;
   f.diag = c.rp.diag;
-  int rc = solve(w, n, sa, w->cond, s);
+  const bool fixed = c.fixed_steps > 0;
+  int rc = fixed ? solve_fixed(w, n, FixedArgs{-1, c.fixed_method, c.fixed_steps, rows}, w->cond, s) : solve(w, n, sa, w->cond, s);
   if (rc) return rc;
   hipLaunchKernelGGL(flow_propose_kernel, dim3(grid4(rows)), dim3(256), 0, s, f);
   // forward solve of the proposal (:269 / :250)
   pad_rows(c.z_fwd, rows, n.d, n.dp, w->zp, s);
   sa.sign = 1; sa.rp.solve = 1;
-  rc = solve(w, n, sa, w->cond, s);
+  rc = fixed ? solve_fixed(w, n, FixedArgs{1, c.fixed_method, c.fixed_steps, rows}, w->cond, s) : solve(w, n, sa, w->cond, s);
   if (rc) return rc;
   if (n.T.kind == MFM_TARGET_LGCP) launch_gemm(kinv(n, w->Y, w->kv, rows, true), s);
   hipLaunchKernelGGL(flow_accept_kernel, dim3(grid4(rows)), dim3(256), 0, s, f);
