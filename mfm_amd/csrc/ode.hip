@@ -5,7 +5,8 @@
 // (independent / random-walk MH in latent space) and the third-party integrator they call,
 // jax.experimental.ode.odeint (:13,345-349; restated in oracle/ode.py): same tableau, same
 // controller (RMS error ratio over d+1 components, accept <= 1, factor clip(0.9 r^-1/5, dfactor, 10)), same initial
-// step heuristic, output at t = 1 by the 4th-order interpolant of the last accepted step.  Each chain runs its OWN
+// step heuristic, output at t = 1 by the 4th-order interpolant of the last accepted step.  The per-row arithmetic of
+// all four solver families (this file, ode_d2.hip, ode_fast.hip, wide.hip) is in dopri5.hip.h.  Each chain runs its OWN
 // adaptive sequence (its own t, dt); the 16 chains of a tile execute in masked lock-step like a vmapped while_loop.
 //
 // Per RHS evaluation the tile pushes value AND tangent rows through the MLP together (forward-mode, M = 32 rows for
@@ -17,6 +18,7 @@
 // The intermediate output times of the "4-mode" example (n_ts = 5) do not change the step sequence (steps are not
 // clamped to output times); they only reset odeint's attempted-step counter, so mxstep is applied per segment as
 // mxstep * (n_ts - 1) attempted steps in total.
+#include "dopri5.hip.h"
 #include "mlp.hip.h"
 #include "prng.hip.h"
 
@@ -145,14 +147,6 @@ __host__ __device__ inline OdeLds ode_lds_layout(const NetDev& n, int NW) {
   L.total = o;
   return L;
 }
-
-// Dormand-Prince tableau (oracle/ode.py)
-__device__ static const float DP_E[7] = {(float)(35.0 / 384 - 1951.0 / 21600), 0.f, (float)(500.0 / 1113 - 22642.0 / 50085),
-                                         (float)(125.0 / 192 - 451.0 / 720), (float)(-2187.0 / 6784 + 12231.0 / 42400),
-                                         (float)(11.0 / 84 - 649.0 / 6300), (float)(-1.0 / 60)};
-__device__ static const float DP_M[7] = {(float)(6025192743.0 / 30085553152.0 / 2), 0.f, (float)(51252292925.0 / 65400821598.0 / 2),
-                                         (float)(-2691868925.0 / 45128329728.0 / 2), (float)(187940372067.0 / 1594534317056.0 / 2),
-                                         (float)(-1776094331.0 / 19743644256.0 / 2), (float)(11237099.0 / 235043384.0 / 2)};
 
 #ifdef MFM_STAMPS
 __device__ unsigned long long* g_flow_dbg = nullptr;     // [WG][8]: cycles, realtime ticks, field evaluations, ...
@@ -597,6 +591,8 @@ struct OdeTile {
   }
 };
 
+enum { RS_T = 0, RS_DT = 1, RS_H0 = 2, RS_D1 = 3, RS_ELL = 4, RS_KL = 5 /* ..11 */, RS_NATT = 12, RS_DONE = 13, RS_FLAG = 14, RS_SFRAC = 15 };
+
 // Integrate the augmented ODE from t = 0 to 1 for the tile whose start positions are in y[][] (accumulator layout);
 // on return y holds the interpolated positions at t = 1, ell the log-det, natt the attempted steps per row.
 // Requires: bZ filled (probe, zero where col >= d), pads of bX / bZ zero, tangent rows of bCat[:, hx2:] zero.
@@ -604,18 +600,6 @@ struct OdeTile {
 // ONE call site of the field evaluation, driven by a small state machine (phase 0: f0, phase 1: the extra
 // evaluation of the initial-step heuristic, phases 2..7: the six Runge-Kutta stages), so the kernel carries one copy
 // of the MLP code; stage results are routed into k[.] with predicated moves (static register indices).
-__device__ static const float DP_TAB[8][7] = {   // [phase][j]: input = y + h * sum_j TAB[phase][j] k_j ; last column: time fraction
-    {0, 0, 0, 0, 0, 0, 0.f},
-    {1, 0, 0, 0, 0, 0, 1.f},
-    {1.f / 5, 0, 0, 0, 0, 0, 1.f / 5},
-    {3.f / 40, 9.f / 40, 0, 0, 0, 0, 3.f / 10},
-    {44.f / 45, -56.f / 15, 32.f / 9, 0, 0, 0, 4.f / 5},
-    {19372.f / 6561, -25360.f / 2187, 64448.f / 6561, -212.f / 729, 0, 0, 8.f / 9},
-    {9017.f / 3168, -355.f / 33, 46732.f / 5247, 49.f / 176, -5103.f / 18656, 0, 1.f},
-    {35.f / 384, 0, 500.f / 1113, 125.f / 192, -2187.f / 6784, 11.f / 84, 1.f}};
-
-enum { RS_T = 0, RS_DT = 1, RS_H0 = 2, RS_D1 = 3, RS_ELL = 4, RS_KL = 5 /* ..11 */, RS_NATT = 12, RS_DONE = 13, RS_FLAG = 14, RS_SFRAC = 15 };
-
 template <int TPW, int NW>
 __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float atol, int max_attempts,
                                           float (&y)[TPW][4], float (&ell)[4], int (&natt)[4], const Replay& rp, int rp_solve, int rp_row0) {
@@ -735,7 +719,7 @@ __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float
       for (int i = 0; i < 4; ++i) {
         const float a1 = dlv[i] / atol;                                // ell0 = 0 -> scale = atol
         const float d0 = sqrtf(p0[i]); d1[i] = sqrtf(p1[i] + a1 * a1);
-        h0[i] = (d0 < 1e-5f || d1[i] < 1e-5f) ? 1e-6f : 0.01f * d0 / d1[i];
+        h0[i] = dp_h0(d0, d1[i]);
       }
       T.rs_put(RS_H0, h0); T.rs_put(RS_D1, d1);
       __syncthreads();
@@ -760,14 +744,8 @@ __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float
       for (int i = 0; i < 4; ++i) {
         const float a2 = (dlv[i] - kl0[i]) / atol;
         const float d2 = sqrtf(p2[i] + a2 * a2) / h04[i];
-        const float h1 = (d14[i] <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h04[i] * 1e-3f)
-                                                            : powf(0.01f / fmaxf(d14[i], d2), 0.2f);
-        dt[i] = fminf(100.f * h04[i], h1);
-        if (rp.dt) {
-          const size_t o = rp.at(rp_solve, rp_row0 + 4 * g + i, 0);
-          if (wave == 0 && c == 0) rp.dt_own[o] = dt[i];
-          dt[i] = rp.dt[o];
-        }
+        dt[i] = dp_dt0(h04[i], d14[i], d2);
+        if (rp.dt) dt[i] = dp_replay_dt0(rp, rp.at(rp_solve, rp_row0 + 4 * g + i, 0), wave == 0 && c == 0, dt[i]);
         any |= (dt[i] > 0.f);
       }
       T.rs_put(RS_DT, dt);
@@ -817,17 +795,8 @@ __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float
         const float rr = el / tol;
         const float ratio = sqrtf((e2[i] + rr * rr) * inv_n);
         bool acc = active && ratio <= 1.f;
-        const float dfac = ratio < 1.f ? 1.f : 0.2f;
-        const float fac = fminf(10.f, fmaxf(0.9f * powf(ratio, -0.2f), dfac));
-        float ndt = fmaxf(ratio == 0.f ? dti * 10.f : dti * fac, 0.f);
-        if (rp.dt && active) {
-          const int j = (int)na4[i];
-          const bool in = j < rp.cap, nx = j + 1 < rp.cap;
-          const size_t o = rp.at(rp_solve, rp_row0 + 4 * g + i, in ? j : 0);
-          if (wave == 0 && c == 0 && in) { rp.ratio[o] = ratio; if (nx) rp.dt_own[o + 1] = ndt; }
-          acc = in && rp.acc[o] != 0;
-          ndt = nx ? rp.dt[o + 1] : 0.f;
-        }
+        float ndt = dp_next_dt(ratio, dti);
+        if (rp.dt && active) dp_replay_attempt(rp, rp.at(rp_solve, rp_row0 + 4 * g + i, 0), wave == 0 && c == 0, (int)na4[i], ratio, acc, ndt);
         t_n[i] = t4[i]; ell_n[i] = ell4[i]; kl0_n[i] = kl[0][i]; dn_n[i] = dn4[i];
         if (acc) {
           const float tn = t4[i] + dti;
@@ -837,21 +806,13 @@ __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float
             float lm = 0.f;
 #pragma unroll
             for (int j = 0; j < 7; ++j) lm += DP_M[j] * kl[j][i];
-            const float y0 = ell4[i], y1 = l1, ym = y0 + dti * lm, f0 = dti * kl[0][i], f1 = dti * kl[6][i];
-            const float pa = -2.f * f0 + 2.f * f1 - 8.f * y0 - 8.f * y1 + 16.f * ym;
-            const float pb = 5.f * f0 - 3.f * f1 + 18.f * y0 + 14.f * y1 - 32.f * ym;
-            const float pc = -4.f * f0 + f1 - 11.f * y0 - 5.f * y1 + 16.f * ym;
-            ell_n[i] = (((pa * sfrac + pb) * sfrac + pc) * sfrac + f0) * sfrac + y0;
+            ell_n[i] = dp_dense(ell4[i], l1, ell4[i] + dti * lm, dti * kl[0][i], dti * kl[6][i], sfrac);
 #pragma unroll
             for (int q = 0; q < TPW; ++q) {
               float km = 0.f;
 #pragma unroll
               for (int j = 0; j < 7; ++j) km += DP_M[j] * k[j][q][i];
-              const float x0 = y[q][i], x1 = xin[q][i], xm = x0 + dti * km, g0 = dti * k[0][q][i], g1 = dti * k[6][q][i];
-              const float qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-              const float qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-              const float qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-              y[q][i] = (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0;
+              y[q][i] = dp_dense(y[q][i], xin[q][i], y[q][i] + dti * km, dti * k[0][q][i], dti * k[6][q][i], sfrac);
             }
             dn_n[i] = 1.f;
           } else {

@@ -547,7 +547,7 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
       }
       const float a1 = dlv / atol;                                     // ell0 = 0 -> scale = atol
       const float d0 = sqrtf(p0); d1 = sqrtf(p1 + a1 * a1);
-      h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+      h0 = dp_h0(d0, d1);
       phase = 1;
     } else if (phase == 1) {
       float p2 = 0.f;
@@ -559,13 +559,8 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
       }
       const float a2 = (dlv - kl[0]) / atol;
       const float d2 = sqrtf(p2 + a2 * a2) / h0;
-      const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-      dt = fminf(100.f * h0, h1);
-      if (rp.dt) {
-        const size_t o = rp.at(rp_solve, rp_row, 0);
-        if (T.writer()) rp.dt_own[o] = dt;
-        dt = rp.dt[o];
-      }
+      dt = dp_dt0(h0, d1, d2);
+      if (rp.dt) dt = dp_replay_dt0(rp, rp.at(rp_solve, rp_row, 0), T.writer(), dt);
       phase = 2;
       if (!__syncthreads_or(dt > 0.f ? 1 : 0)) break;
     } else if (phase < 7) {
@@ -596,17 +591,8 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
       const float rr = el / tol;
       const float ratio = sqrtf((e2 + rr * rr) * inv_n);
       bool acc = active && ratio <= 1.f;
-      const float dfac = ratio < 1.f ? 1.f : 0.2f;
-      const float fac = fminf(10.f, fmaxf(0.9f * powf(ratio, -0.2f), dfac));
-      float ndt = fmaxf(ratio == 0.f ? dti * 10.f : dti * fac, 0.f);
-      if (rp.dt && active) {
-        const int j = (int)na;
-        const bool in = j < rp.cap, nx = j + 1 < rp.cap;
-        const size_t o = rp.at(rp_solve, rp_row, in ? j : 0);
-        if (T.writer() && in) { rp.ratio[o] = ratio; if (nx) rp.dt_own[o + 1] = ndt; }
-        acc = in && rp.acc[o] != 0;
-        ndt = nx ? rp.dt[o + 1] : 0.f;
-      }
+      float ndt = dp_next_dt(ratio, dti);
+      if (rp.dt && active) dp_replay_attempt(rp, rp.at(rp_solve, rp_row, 0), T.writer(), (int)na, ratio, acc, ndt);
       if (acc) {
         const float tn = t + dti;
         if (tn >= 1.f) {
@@ -615,21 +601,13 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
           float lm = 0.f;
 #pragma unroll
           for (int j = 0; j < 7; ++j) lm += DP_M[j] * kl[j];
-          const float y0 = ell, y1 = l1, ym = y0 + dti * lm, f0 = dti * kl[0], f1 = dti * kl[6];
-          const float pa = -2.f * f0 + 2.f * f1 - 8.f * y0 - 8.f * y1 + 16.f * ym;
-          const float pb = 5.f * f0 - 3.f * f1 + 18.f * y0 + 14.f * y1 - 32.f * ym;
-          const float pc = -4.f * f0 + f1 - 11.f * y0 - 5.f * y1 + 16.f * ym;
-          ell = (((pa * sfrac + pb) * sfrac + pc) * sfrac + f0) * sfrac + y0;
+          ell = dp_dense(ell, l1, ell + dti * lm, dti * kl[0], dti * kl[6], sfrac);
 #pragma unroll
           for (int q = 0; q < 2; ++q) {
             float km = 0.f;
 #pragma unroll
             for (int j = 0; j < 7; ++j) km += DP_M[j] * k[j][q];
-            const float x0 = y[q], x1 = xin[q], xm = x0 + dti * km, g0 = dti * k[0][q], g1 = dti * k[6][q];
-            const float qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-            const float qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-            const float qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-            y[q] = (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0;
+            y[q] = dp_dense(y[q], xin[q], y[q] + dti * km, dti * k[0][q], dti * k[6][q], sfrac);
           }
           done = true;
         } else {
@@ -655,22 +633,21 @@ __device__ __forceinline__ void solve(TILE& T, float rtol, float atol, int max_a
 // evaluation, no controller.  The time batch is the one of an attempt: prepare() takes five stage times -- two RK4 steps (t, t + h/2,
 // t + h, t + 3h/2, t + 2h) or five Euler steps -- and eval() reads slot s at phase 2 + s (phases 2 .. 6: the streamed tile
 // re-evaluates its time branch in each, as it reuses it at phase 7 only).  Oracle: oracle/ode.py: odeint_fixed.
-enum { FIX_RK4 = 1, FIX_EULER = 2 };      // = MFM_ODE_RK4 / MFM_ODE_EULER
 template <int METHOD, typename TILE>
 __device__ __forceinline__ void solve_fixed(TILE& T, int nsteps, float (&y)[2], float& ell) {
-  constexpr int SPB = METHOD == FIX_RK4 ? 2 : 5;       // steps per time batch
+  constexpr int SPB = METHOD == MFM_ODE_RK4 ? 2 : 5;       // steps per time batch
   const float h = 1.f / (float)nsteps;
   float el = 0.f;
 #pragma unroll 1
   for (int n0 = 0; n0 < nsteps; n0 += SPB) {
     float ts5[5];
 #pragma unroll
-    for (int s = 0; s < 5; ++s) ts5[s] = METHOD == FIX_RK4 ? ((float)(2 * n0 + s) * 0.5f) * h : (float)(n0 + s) * h;
+    for (int s = 0; s < 5; ++s) ts5[s] = METHOD == MFM_ODE_RK4 ? ((float)(2 * n0 + s) * 0.5f) * h : (float)(n0 + s) * h;
     T.prepare(ts5);
 #pragma unroll 1
     for (int ss = 0; ss < SPB && n0 + ss < nsteps; ++ss) {
       float kv[2], dl;
-      if constexpr (METHOD == FIX_EULER) {
+      if constexpr (METHOD == MFM_ODE_EULER) {
         T.eval(y[0], y[1], ts5[ss], kv, dl, 2 + ss);
         y[0] = fmaf(h, kv[0], y[0]); y[1] = fmaf(h, kv[1], y[1]);
         el = fmaf(h, dl, el);
@@ -694,7 +671,7 @@ __device__ __forceinline__ void solve_fixed(TILE& T, int nsteps, float (&y)[2], 
   ell = el;
 }
 
-// METHOD 0: the adaptive solve (the kernels of the adaptive path); FIX_RK4 / FIX_EULER: a.fixed_steps equal steps
+// METHOD 0: the adaptive solve (the kernels of the adaptive path); MFM_ODE_RK4 / MFM_ODE_EULER: a.fixed_steps equal steps
 template <typename TILE, int METHOD = 0>
 __global__ __launch_bounds__(NW * 64) void transform_kernel(OdeArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -834,8 +811,8 @@ static int launch_fixed_m(const OdeArgs& a, const FlowArgs* f, hipStream_t strea
   return f ? launch_flow_t<Tile, METHOD>(a, *f, sm, stream) : launch_transform_t<Tile, METHOD>(a, sm, stream);
 }
 static int launch_fixed(const OdeArgs& a, const FlowArgs* f, hipStream_t stream) {
-  if (a.fixed_method == FIX_RK4) return launch_fixed_m<FIX_RK4>(a, f, stream);
-  if (a.fixed_method == FIX_EULER) return launch_fixed_m<FIX_EULER>(a, f, stream);
+  if (a.fixed_method == MFM_ODE_RK4) return launch_fixed_m<MFM_ODE_RK4>(a, f, stream);
+  if (a.fixed_method == MFM_ODE_EULER) return launch_fixed_m<MFM_ODE_EULER>(a, f, stream);
   return -4;
 }
 

@@ -951,7 +951,7 @@ __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int m
         const float dl0 = sum8(S::DLP + 0 * 128);
         const float a1 = dl0 / atol;                                   // ell0 = 0 -> scale = atol
         const float d0 = sqrtf(sum8(S::RED + 0 * 128)), d1 = sqrtf(sum8(S::RED + 1 * 128) + a1 * a1);
-        R1(RS_H0) = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+        R1(RS_H0) = dp_h0(d0, d1);
         R1(RS_D1) = d1; R1(RS_KL + 0) = dl0;
       }
       __syncthreads();
@@ -978,9 +978,8 @@ __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int m
         const float h0 = R1(RS_H0), d1 = R1(RS_D1);
         const float a2 = (sum8(S::DLP + 1 * 128) - R1(RS_KL + 0)) / atol;
         const float d2 = sqrtf(sum8(S::RED + 2 * 128) + a2 * a2) / h0;
-        const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-        float dt = fminf(100.f * h0, h1);
-        if constexpr (RP) { const size_t o = rp.at(0, rp_row0 + T.lane, 0); rp.dt_own[o] = dt; dt = rp.dt[o]; }
+        float dt = dp_dt0(h0, d1, d2);
+        if constexpr (RP) dt = dp_replay_dt0(rp, rp.at(0, rp_row0 + T.lane, 0), true, dt);
         R1(RS_DT) = dt;
         any = dt > 0.f ? 1 : 0;
       }
@@ -1040,36 +1039,17 @@ __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int m
         const float rr = el / tol;
         const float ratio = sqrtf((e2 + rr * rr) * inv_n);
         bool acc = active && ratio <= 1.f;
-        const float dfac = ratio < 1.f ? 1.f : 0.2f;
-#ifdef MFM_LIB_POW
-        const float fac = fminf(10.f, fmaxf(0.9f * powf(ratio, -0.2f), dfac));
-#else
-    // ratio^(-1/5) through the hardware's log2 / exp2 (1 ulp each; ratio is a non-negative finite number or NaN here): the library's
-    // powf spends ~150 dependent instructions on cases this call cannot meet, on ONE wave while the other seven wait at the barrier
-        const float fac = fminf(10.f, fmaxf(0.9f * __builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(ratio)), dfac));
-#endif
-        float ndt = fmaxf(ratio == 0.f ? dti * 10.f : dti * fac, 0.f);
+        float ndt = dp_next_dt<true>(ratio, dti);      // (the hardware power: see dp_next_dt)
         if constexpr (RP) {
-          if (active) {
-            const int j = (int)na;
-            const bool in = j < rp.cap, nx = j + 1 < rp.cap;
-            const size_t o = rp.at(0, rp_row0 + T.lane, in ? j : 0);
-            if (in) { rp.ratio[o] = ratio; if (nx) rp.dt_own[o + 1] = ndt; }
-            acc = in && rp.acc[o] != 0;
-            ndt = nx ? rp.dt[o + 1] : 0.f;
-          }
+          if (active) dp_replay_attempt(rp, rp.at(0, rp_row0 + T.lane, 0), true, (int)na, ratio, acc, ndt);
         }
         const float tn = t0 + dti;
         const bool fin = acc && tn >= 1.f, adv = acc && !(tn >= 1.f);
         const float sfrac = (1.f - t0) / (tn - t0);
-        // log-det: 4th-order interpolant of this step evaluated at t = 1 when the step reaches the end
-        const float y0 = ell0, ym = y0 + dti * lm, f0 = dti * kl[0], f1 = dti * kl[6];
-        const float pa = -2.f * f0 + 2.f * f1 - 8.f * y0 - 8.f * l1 + 16.f * ym;
-        const float pb = 5.f * f0 - 3.f * f1 + 18.f * y0 + 14.f * l1 - 32.f * ym;
-        const float pc = -4.f * f0 + f1 - 11.f * y0 - 5.f * l1 + 16.f * ym;
-        const float li = (((pa * sfrac + pb) * sfrac + pc) * sfrac + f0) * sfrac + y0;
         const float dt_n = active ? ndt : dti, na_n = active ? na + 1.f : na, dn_n = fin ? 1.f : dn;
-        R1(RS_T) = acc ? tn : t0; R1(RS_DT) = dt_n; R1(RS_ELL) = fin ? li : (adv ? l1 : ell0);
+        R1(RS_T) = acc ? tn : t0; R1(RS_DT) = dt_n;
+        // log-det: 4th-order interpolant of this step evaluated at t = 1 when the step reaches the end
+        R1(RS_ELL) = fin ? dp_dense(ell0, l1, ell0 + dti * lm, dti * kl[0], dti * kl[6], sfrac) : (adv ? l1 : ell0);
         R1(RS_KL + 0) = adv ? kl[6] : kl[0]; R1(RS_NATT) = na_n; R1(RS_DONE) = dn_n;
         R1(RS_FLAG) = fin ? 2.f : (adv ? 1.f : 0.f); R1(RS_SFRAC) = sfrac;
         any = (dn_n == 0.f && na_n < (float)max_attempts && dt_n > 0.f) ? 1 : 0;
@@ -1089,12 +1069,8 @@ __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int m
             for (int j = 0; j < 6; ++j) acc += DP_TAB[7][j] * k[j][q][i];
 #pragma unroll
             for (int j = 0; j < 7; ++j) km += DP_M[j] * k[j][q][i];
-            const float x0 = y[q][i], x1 = x0 + dti * acc, xm = x0 + dti * km, g0 = dti * k[0][q][i], g1 = dti * k[6][q][i];
-            const float qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-            const float qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-            const float qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-            const float xi = (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0;
-            y[q][i] = fin ? xi : (adv ? x1 : x0);
+            const float x0 = y[q][i], x1 = x0 + dti * acc;
+            y[q][i] = fin ? dp_dense(x0, x1, x0 + dti * km, dti * k[0][q][i], dti * k[6][q][i], sfrac) : (adv ? x1 : x0);
             k[0][q][i] = adv ? k[6][q][i] : k[0][q][i];
           }
         }
@@ -1151,7 +1127,7 @@ __device__ __forceinline__ int leaders_end_of_attempt(FTile<D>& T, const AA& a, 
     const float dl0 = dlsum(S::DLP + 1 * 128);
     const float a1 = dl0 / atol;
     const float d0 = sqrtf(sum8(S::RED + 0 * 128)), d1 = sqrtf(sum8(S::RED + 1 * 128) + a1 * a1);
-    const float h0 = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+    const float h0 = dp_h0(d0, d1);
     R1(RS_H0) = h0; R1(RS_D1) = d1; R1(RS_KL + 0) = dl0;
     R1(RS_DT) = h0; R1(RS_MODE) = (float)RM_INIT1;
     flag = 3.f;
@@ -1159,9 +1135,8 @@ __device__ __forceinline__ int leaders_end_of_attempt(FTile<D>& T, const AA& a, 
     const float h0 = R1(RS_H0), d1 = R1(RS_D1);
     const float a2 = (dlsum(S::DLP + 1 * 128) - R1(RS_KL + 0)) / atol;
     const float d2 = sqrtf(sum8(S::RED + 2 * 128) + a2 * a2) / h0;
-    const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-    float dt = fminf(100.f * h0, h1);
-    if constexpr (RP) { const size_t o = a.rp.at((int)R1(RS_SOLVE), b0 + ln, 0); a.rp.dt_own[o] = dt; dt = a.rp.dt[o]; }
+    float dt = dp_dt0(h0, d1, d2);
+    if constexpr (RP) dt = dp_replay_dt0(a.rp, a.rp.at((int)R1(RS_SOLVE), b0 + ln, 0), true, dt);
     R1(RS_DT) = dt; R1(RS_MODE) = (float)RM_ATT;
     flag = 0.f;
   } else if (mode == (float)RM_ATT) {
@@ -1185,33 +1160,15 @@ __device__ __forceinline__ int leaders_end_of_attempt(FTile<D>& T, const AA& a, 
     const float rr = el / tol;
     const float ratio = sqrtf((e2 + rr * rr) * inv_n);
     bool acc = active && ratio <= 1.f;
-    const float dfac = ratio < 1.f ? 1.f : 0.2f;
-#ifdef MFM_LIB_POW
-    const float fac = fminf(10.f, fmaxf(0.9f * powf(ratio, -0.2f), dfac));
-#else
-    const float fac = fminf(10.f, fmaxf(0.9f * __builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(ratio)), dfac));      // (see solve)
-#endif
-    float ndt = fmaxf(ratio == 0.f ? dti * 10.f : dti * fac, 0.f);
+    float ndt = dp_next_dt<true>(ratio, dti);
     if constexpr (RP) {
-      if (active) {
-        const int j = (int)na;
-        const bool in = j < a.rp.cap, nx = j + 1 < a.rp.cap;
-        const size_t o = a.rp.at((int)R1(RS_SOLVE), b0 + ln, in ? j : 0);
-        if (in) { a.rp.ratio[o] = ratio; if (nx) a.rp.dt_own[o + 1] = ndt; }
-        acc = in && a.rp.acc[o] != 0;
-        ndt = nx ? a.rp.dt[o + 1] : 0.f;
-      }
+      if (active) dp_replay_attempt(a.rp, a.rp.at((int)R1(RS_SOLVE), b0 + ln, 0), true, (int)na, ratio, acc, ndt);
     }
     const float tn = t0 + dti;
     const bool fin = acc && tn >= 1.f, adv = acc && !(tn >= 1.f);
     const float sfrac = (1.f - t0) / (tn - t0);
-    const float y0 = ell0, ym = y0 + dti * lm, f0 = dti * kl[0], f1 = dti * kl[6];
-    const float pa = -2.f * f0 + 2.f * f1 - 8.f * y0 - 8.f * l1 + 16.f * ym;
-    const float pb = 5.f * f0 - 3.f * f1 + 18.f * y0 + 14.f * l1 - 32.f * ym;
-    const float pc = -4.f * f0 + f1 - 11.f * y0 - 5.f * l1 + 16.f * ym;
-    const float li = (((pa * sfrac + pb) * sfrac + pc) * sfrac + f0) * sfrac + y0;
     const float dt_n = active ? ndt : dti, na_n = active ? na + 1.f : na;
-    const float ell_n = fin ? li : (adv ? l1 : ell0);
+    const float ell_n = fin ? dp_dense(ell0, l1, ell0 + dti * lm, dti * kl[0], dti * kl[6], sfrac) : (adv ? l1 : ell0);
     // the solve ends when t reaches 1, or (as in odeint's while_loop) when the step budget / step size runs out
     const bool over = fin || !(na_n < (float)max_attempts && dt_n > 0.f);
     flag = fin ? 2.f : (adv ? 1.f : 0.f);
@@ -1746,11 +1703,7 @@ __device__ __noinline__ void solve2_tail(TailArgs a, int b0) {
           float kmid = 0.f;
 #pragma unroll
           for (int j = 0; j < 7; ++j) kmid += DP_M[j] * km[p][j][q];
-          const float xm = x0 + hs[p] * kmid, g0 = hs[p] * km[p][0][q], g1 = hs[p] * km[p][6][q];
-          const float qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-          const float qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-          const float qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-          xi = (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0;
+          xi = dp_dense(x0, x1, x0 + hs[p] * kmid, hs[p] * km[p][0][q], hs[p] * km[p][6][q], sfrac);
         }
         float yn = fin ? xi : (adv ? x1 : x0);
         km[p][0][q] = ini ? km[p][1][q] : (adv ? km[p][6][q] : km[p][0][q]);
@@ -2019,11 +1972,7 @@ __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const Flow
             float km = 0.f;
 #pragma unroll
             for (int j = 0; j < 7; ++j) km += DP_M[j] * k[j][q][i];
-            const float xm = x0 + dti * km, g0 = dti * k[0][q][i], g1 = dti * k[6][q][i];
-            const float qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-            const float qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-            const float qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-            xi = (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0;
+            xi = dp_dense(x0, x1, x0 + dti * km, dti * k[0][q][i], dti * k[6][q][i], sfrac);
           }
           float yn = fin ? xi : (adv ? x1 : x0);
           k[0][q][i] = ini ? k[1][q][i] : (adv ? k[6][q][i] : k[0][q][i]);

@@ -13,13 +13,11 @@
 // d = 2 four-chain tiles: wide.hip / ode_d2.hip: solve_fixed.
 namespace fast {
 
-enum { ODE_RK4 = 1, ODE_EULER = 2 };
-
 template <int D, int METHOD>
 __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[FTile<D>::TPW][4], float (&ell)[4]) {
   using S = FS<D>;
   constexpr int TPW = FTile<D>::TPW, LDX = S::LDX;
-  constexpr int NK = METHOD == ODE_RK4 ? 4 : 1, SPB = METHOD == ODE_RK4 ? 2 : 5;      // stages per step, steps per time batch
+  constexpr int NK = METHOD == MFM_ODE_RK4 ? 4 : 1, SPB = METHOD == MFM_ODE_RK4 ? 2 : 5;      // stages per step, steps per time batch
   const int wave = T.wave;
   {
     const float z4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -51,7 +49,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
     for (int j = 0; j < NK; ++j) T.part_get(S::DLP + (4 * par + j) * 128, l[j]);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      el[i] += METHOD == ODE_RK4 ? (h / 6.f) * ((l[0][i] + l[NK - 1][i]) + 2.f * (l[NK > 1 ? 1 : 0][i] + l[NK > 2 ? 2 : 0][i])) : h * l[0][i];
+      el[i] += METHOD == MFM_ODE_RK4 ? (h / 6.f) * ((l[0][i] + l[NK - 1][i]) + 2.f * (l[NK > 1 ? 1 : 0][i] + l[NK > 2 ? 2 : 0][i])) : h * l[0][i];
   };
   int par = 0; bool pending = false;
 #pragma unroll 1
@@ -62,7 +60,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
       const double f = (double)T.ffreq;
 #pragma unroll
       for (int s = 0; s < 5; ++s) {
-        const float tt = METHOD == ODE_RK4 ? ((float)(2 * n0 + s) * 0.5f) * h : (float)(n0 + s) * h;
+        const float tt = METHOD == MFM_ODE_RK4 ? ((float)(2 * n0 + s) * 0.5f) * h : (float)(n0 + s) * h;
         const double te = T.sign > 0 ? (double)tt : 1.0 - (double)tt;          // :229
         double ft = f * te;
         ft -= rint(ft);
@@ -84,7 +82,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
         if (pending) { add_ell(par ^ 1); pending = false; }
       }
       float kv[TPW][4];
-      if constexpr (METHOD == ODE_EULER) {
+      if constexpr (METHOD == MFM_ODE_EULER) {
         T.eval(ss, cur, 4 * par, last_of_batch, P, Q, kv, sg);
         cur ^= 1;
 #pragma unroll
@@ -311,13 +309,13 @@ static int launch_transform_fixed_m(const OdeArgs& a0, int nsteps, f32x4* scratc
 }
 static int launch_flow_fixed(const OdeArgs& a, const FlowArgs& f, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
   const bool w256 = tile_width(a.net) == 256;
-  if (method == ODE_RK4) return w256 ? launch_flow_fixed_m<256, ODE_RK4>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, ODE_RK4>(a, f, nsteps, scratch, stream);
-  return w256 ? launch_flow_fixed_m<256, ODE_EULER>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, ODE_EULER>(a, f, nsteps, scratch, stream);
+  if (method == MFM_ODE_RK4) return w256 ? launch_flow_fixed_m<256, MFM_ODE_RK4>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_RK4>(a, f, nsteps, scratch, stream);
+  return w256 ? launch_flow_fixed_m<256, MFM_ODE_EULER>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_EULER>(a, f, nsteps, scratch, stream);
 }
 static int launch_transform_fixed(const OdeArgs& a, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
   const bool w256 = tile_width(a.net) == 256;
-  if (method == ODE_RK4) return w256 ? launch_transform_fixed_m<256, ODE_RK4>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, ODE_RK4>(a, nsteps, scratch, stream);
-  return w256 ? launch_transform_fixed_m<256, ODE_EULER>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, ODE_EULER>(a, nsteps, scratch, stream);
+  if (method == MFM_ODE_RK4) return w256 ? launch_transform_fixed_m<256, MFM_ODE_RK4>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_RK4>(a, nsteps, scratch, stream);
+  return w256 ? launch_transform_fixed_m<256, MFM_ODE_EULER>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_EULER>(a, nsteps, scratch, stream);
 }
 
 }  // namespace fast

@@ -21,6 +21,7 @@
 // Replaces the same reference code as fm.hip / ode.hip: exe_flow_matching.py:56-90 (VectorFieldNet), :151-178 (loss),
 // :206-242 (CNF transforms), :246-278 (flow-MH steps), jax.value_and_grad at :364-365.
 #include <type_traits>
+#include "dopri5.hip.h"
 #include "mlp.hip.h"
 #include "prng.hip.h"
 
@@ -719,22 +720,6 @@ __global__ __launch_bounds__(256) void loss_kernel(LossArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------
 struct RowState { float *t, *dt, *h0, *d1, *ell, *kl /* [7][rows] */; int *natt, *done; };
 
-__device__ static const float W_TAB[8][7] = {   // [phase][j]: input = y + h sum_j TAB[phase][j] k_j ; last column: time fraction
-    {0, 0, 0, 0, 0, 0, 0.f},
-    {1, 0, 0, 0, 0, 0, 1.f},
-    {1.f / 5, 0, 0, 0, 0, 0, 1.f / 5},
-    {3.f / 40, 9.f / 40, 0, 0, 0, 0, 3.f / 10},
-    {44.f / 45, -56.f / 15, 32.f / 9, 0, 0, 0, 4.f / 5},
-    {19372.f / 6561, -25360.f / 2187, 64448.f / 6561, -212.f / 729, 0, 0, 8.f / 9},
-    {9017.f / 3168, -355.f / 33, 46732.f / 5247, 49.f / 176, -5103.f / 18656, 0, 1.f},
-    {35.f / 384, 0, 500.f / 1113, 125.f / 192, -2187.f / 6784, 11.f / 84, 1.f}};
-__device__ static const float W_E[7] = {(float)(35.0 / 384 - 1951.0 / 21600), 0.f, (float)(500.0 / 1113 - 22642.0 / 50085),
-                                        (float)(125.0 / 192 - 451.0 / 720), (float)(-2187.0 / 6784 + 12231.0 / 42400),
-                                        (float)(11.0 / 84 - 649.0 / 6300), (float)(-1.0 / 60)};
-__device__ static const float W_M[7] = {(float)(6025192743.0 / 30085553152.0 / 2), 0.f, (float)(51252292925.0 / 65400821598.0 / 2),
-                                        (float)(-2691868925.0 / 45128329728.0 / 2), (float)(187940372067.0 / 1594534317056.0 / 2),
-                                        (float)(-1776094331.0 / 19743644256.0 / 2), (float)(11237099.0 / 235043384.0 / 2)};
-
 // Parity instrumentation (mfm_debug_replay): the solve runs on a PRESCRIBED step sequence and records its own controller's
 // values; same meaning as `Replay` in ode.hip (dt == nullptr: off, production).
 struct WReplay {
@@ -800,7 +785,7 @@ __global__ __launch_bounds__(256) void stage_prep_kernel(OdeBuf a, int phase) {
   if (cp < 0) return;
   float cf[7];
 #pragma unroll
-  for (int j = 0; j < 7; ++j) cf[j] = W_TAB[phase][j];
+  for (int j = 0; j < 7; ++j) cf[j] = DP_TAB[phase][j];
   const float h = phase == 1 ? a.rs.h0[b] : a.rs.dt[b];
   const float ts = a.rs.t[b] + h * cf[6];
   const size_t o0 = (size_t)b * a.dp, ks = (size_t)a.rows * a.dp, oc = (size_t)cp * a.dp;
@@ -820,7 +805,7 @@ __global__ __launch_bounds__(256) void stage_prep_kernel(OdeBuf a, int phase) {
       const float t0 = a.rs.t[b];
 #pragma unroll 1
       for (int sl = 0; sl < 5; ++sl) {
-        const float tsl = t0 + h * W_TAB[2 + sl][6];
+        const float tsl = t0 + h * DP_TAB[2 + sl][6];
         const double te = a.sign > 0 ? (double)tsl : 1.0 - (double)tsl;
         fourier_row(a.fourier, a.F, a.F2p, te, a.ffat + ((size_t)sl * a.tb_rows + cp) * a.F2p, lane);
       }
@@ -874,7 +859,7 @@ __global__ __launch_bounds__(256) void stage_finish_kernel(OdeBuf a, int phase) 
     if (lane == 0) {
       const float a1 = dl / atol;
       const float d0 = sqrtf(p0), d1 = sqrtf(p1 + a1 * a1);
-      a.rs.h0[b] = (d0 < 1e-5f || d1 < 1e-5f) ? 1e-6f : 0.01f * d0 / d1;
+      a.rs.h0[b] = dp_h0(d0, d1);
       a.rs.d1[b] = d1;
     }
   } else if (phase == 1) {
@@ -890,9 +875,8 @@ __global__ __launch_bounds__(256) void stage_finish_kernel(OdeBuf a, int phase) 
       const float h0 = a.rs.h0[b], d1 = a.rs.d1[b];
       const float a2 = (dl - a.rs.kl[b]) / atol;
       const float d2 = sqrtf(p2 + a2 * a2) / h0;
-      const float h1 = (d1 <= 1e-15f && d2 <= 1e-15f) ? fmaxf(1e-6f, h0 * 1e-3f) : powf(0.01f / fmaxf(d1, d2), 0.2f);
-      float dt = fminf(100.f * h0, h1);
-      if (a.rp.dt) { const size_t o = a.rp.at(b, 0); a.rp.dt_own[o] = dt; dt = a.rp.dt[o]; }
+      float dt = dp_dt0(h0, d1, d2);
+      if (a.rp.dt) dt = dp_replay_dt0(a.rp, a.rp.at(b, 0), true, dt);
       a.rs.dt[b] = dt;
       if (dt > 0.f) atomicAdd(a.n_active, 1);
     }
@@ -908,7 +892,7 @@ __global__ __launch_bounds__(256) void stage_finish_kernel(OdeBuf a, int phase) 
       const size_t o = o0 + col;
       T er = V::zero();
 #pragma unroll
-      for (int j = 0; j < 7; ++j) er += W_E[j] * V::ld(a.K + j * ks + o);
+      for (int j = 0; j < 7; ++j) er += DP_E[j] * V::ld(a.K + j * ks + o);
       er *= dti;
       const T tol = atol + rtol * V::maxv(V::absv(V::ld(a.Y + o)), V::absv(V::ld(a.X + oc + col)));
       const T rr = er / tol;
@@ -918,25 +902,18 @@ __global__ __launch_bounds__(256) void stage_finish_kernel(OdeBuf a, int phase) 
     const bool active = !dn && na < a.max_attempts && dti > 0.f;
     float sl = 0.f, el = 0.f;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) sl += W_TAB[7][j] * kl[j];
+    for (int j = 0; j < 6; ++j) sl += DP_TAB[7][j] * kl[j];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) el += W_E[j] * kl[j];
+    for (int j = 0; j < 7; ++j) el += DP_E[j] * kl[j];
     const float l1 = ell0 + dti * sl;
     el *= dti;
     const float tol = atol + rtol * fmaxf(fabsf(ell0), fabsf(l1));
     const float rr = el / tol;
     const float ratio = sqrtf((e2 + rr * rr) / (float)(a.d + 1));
     bool acc = active && ratio <= 1.f;
-    const float dfac = ratio < 1.f ? 1.f : 0.2f;
-    const float fac = fminf(10.f, fmaxf(0.9f * powf(ratio, -0.2f), dfac));
-    float ndt = fmaxf(ratio == 0.f ? dti * 10.f : dti * fac, 0.f);
-    if (a.rp.dt && active) {               // every lane of the wavefront takes the same (uniform) decision
-      const bool in = na < a.rp.cap, nx = na + 1 < a.rp.cap;
-      const size_t o = a.rp.at(b, in ? na : 0);
-      if (lane == 0 && in) { a.rp.ratio[o] = ratio; if (nx) a.rp.dt_own[o + 1] = ndt; }
-      acc = in && a.rp.acc[o] != 0;
-      ndt = nx ? a.rp.dt[o + 1] : 0.f;
-    }
+    float ndt = dp_next_dt(ratio, dti);
+    // every lane of the wavefront takes the same (uniform) decision
+    if (a.rp.dt && active) dp_replay_attempt(a.rp, a.rp.at(b, 0), lane == 0, na, ratio, acc, ndt);
     float t_n = t0, ell_n = ell0, kl0_n = kl[0];
     int dn_n = dn;
     if (acc) {
@@ -945,24 +922,15 @@ __global__ __launch_bounds__(256) void stage_finish_kernel(OdeBuf a, int phase) 
         const float sfrac = (1.f - t0) / (tn - t0);
         float lm = 0.f;
 #pragma unroll
-        for (int j = 0; j < 7; ++j) lm += W_M[j] * kl[j];
-        {
-          const float y0 = ell0, y1 = l1, ym = y0 + dti * lm, f0 = dti * kl[0], f1 = dti * kl[6];
-          const float pa = -2.f * f0 + 2.f * f1 - 8.f * y0 - 8.f * y1 + 16.f * ym;
-          const float pb = 5.f * f0 - 3.f * f1 + 18.f * y0 + 14.f * y1 - 32.f * ym;
-          const float pc = -4.f * f0 + f1 - 11.f * y0 - 5.f * y1 + 16.f * ym;
-          ell_n = (((pa * sfrac + pb) * sfrac + pc) * sfrac + f0) * sfrac + y0;
-        }
+        for (int j = 0; j < 7; ++j) lm += DP_M[j] * kl[j];
+        ell_n = dp_dense(ell0, l1, ell0 + dti * lm, dti * kl[0], dti * kl[6], sfrac);
         for (int col = lane * V::W; col < a.d; col += 64 * V::W) {
           const size_t o = o0 + col;
           T km = V::zero();
 #pragma unroll
-          for (int j = 0; j < 7; ++j) km += W_M[j] * V::ld(a.K + j * ks + o);
-          const T x0 = V::ld(a.Y + o), x1 = V::ld(a.X + oc + col), xm = x0 + dti * km, g0 = dti * V::ld(a.K + o), g1 = dti * V::ld(a.K + 6 * ks + o);
-          const T qa = -2.f * g0 + 2.f * g1 - 8.f * x0 - 8.f * x1 + 16.f * xm;
-          const T qb = 5.f * g0 - 3.f * g1 + 18.f * x0 + 14.f * x1 - 32.f * xm;
-          const T qc = -4.f * g0 + g1 - 11.f * x0 - 5.f * x1 + 16.f * xm;
-          V::st(a.Y + o, (((qa * sfrac + qb) * sfrac + qc) * sfrac + g0) * sfrac + x0);
+          for (int j = 0; j < 7; ++j) km += DP_M[j] * V::ld(a.K + j * ks + o);
+          const T x0 = V::ld(a.Y + o);
+          V::st(a.Y + o, dp_dense<T>(x0, V::ld(a.X + oc + col), x0 + dti * km, dti * V::ld(a.K + o), dti * V::ld(a.K + 6 * ks + o), sfrac));
         }
         dn_n = 1;
       } else {
@@ -1744,7 +1712,6 @@ static int solve(Ctx* w, const NetDev& n, const SolveArgs& c, float* xstage, hip
 // derivative, divergence term; at the step's last stage the step combination).  The time branch is batched as in the adaptive
 // loop: one GEMM chain on 5 rows-row slots serves two RK4 steps (t, t + h/2, t + h, t + 3h/2, t + 2h) or five Euler steps.
 // Oracle: oracle/ode.py: odeint_fixed.
-enum { FIX_RK4 = 1, FIX_EULER = 2 };      // = MFM_ODE_RK4 / MFM_ODE_EULER
 struct FixBuf {
   int rows, d, dp, F, F2p, sign, method;
   float h;
@@ -1791,7 +1758,7 @@ __global__ __launch_bounds__(256) void fixed_finish_kernel(FixBuf a, int j, int 
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.rows) return;
   const size_t o0 = (size_t)b * a.dp, ks = (size_t)a.rows * a.dp;
-  const bool rk4 = a.method == FIX_RK4;
+  const bool rk4 = a.method == MFM_ODE_RK4;
   const float h = a.h, h6 = a.h / 6.f;
   float dpart = 0.f;
   for (int col = lane * V::W; col < a.d; col += 64 * V::W) {
@@ -1833,8 +1800,8 @@ struct FixedArgs { int sign, method, nsteps, rows; };
 // w->Y, w->rs.ell, w->rs.natt (= nsteps).  Launches only: no synchronisation, no device-to-host copy.
 static int solve_fixed(Ctx* w, const NetDev& n, const FixedArgs& c, float* xstage, hipStream_t s) {
   const int rows = c.rows, N = c.nsteps;
-  if (N < 1 || (c.method != FIX_RK4 && c.method != FIX_EULER)) return -3;
-  const bool exact = w->exact, rk4 = c.method == FIX_RK4;
+  if (N < 1 || (c.method != MFM_ODE_RK4 && c.method != MFM_ODE_EULER)) return -3;
+  const bool exact = w->exact, rk4 = c.method == MFM_ODE_RK4;
   const int fmode = exact ? 2 : 1;
   if (exact) {
     if (!w->master || jt_alloc(w, n)) return -4;
