@@ -104,7 +104,9 @@ int mfm_sync(mfm_ctx* ctx);
 int mfm_num_params(const mfm_ctx* ctx);                        /* P_w + P_b */
 
 /* ---- target (distributions.py) ---------------------------------------------------------------------------------
- * MFM_PHI4: h_params = {a, beta}                                    (PhiFour.__init__, :115-129)
+ * MFM_PHI4: h_params = {a, beta}                                    (PhiFour.__init__, :115-129; Dirichlet 0)
+ *           or {a, beta, bc_kind, bc_value}: bc_kind 0 = Dirichlet, both ends held at bc_value (finite);
+ *           1 = periodic ring, bc_value ignored.  Any other kind: MFM_EINVAL.
  * MFM_GMM : h_params = {n_modes, modes[K*d], stds[K*d], weights[K]} (GaussianMixture, :43-56; stds = sqrt(covs))
  * MFM_LGCP: h_params = {mu, poisson_a, log_norm, counts[d], Kinv[d*d]}  (LogGaussianCoxPines, :233-281) */
 int mfm_set_target(mfm_ctx* ctx, int kind, const double* h_params, size_t n);

@@ -417,8 +417,16 @@ extern "C" int mfm_set_target(mfm_ctx* x, int kind, const double* p, size_t np) 
   memset(&T, 0, sizeof T);
   T.kind = kind; T.dim = d;
   if (kind == MFM_PHI4) {
-    if (np != 2) return fail(MFM_EINVAL, "phi4 target takes {a, beta}");
+    if (np != 2 && np != 4) return fail(MFM_EINVAL, "phi4 target takes {a, beta} or {a, beta, bc_kind, bc_value}");
     T.coef = (float)(p[0] * d); T.tbeta = (float)p[1];
+    if (np == 4) {      // boundary (distributions.py:130-139): kind 0 = Dirichlet at bc_value, 1 = periodic (bc_value ignored)
+      if (p[2] != 0.0 && p[2] != 1.0) return fail(MFM_EINVAL, "phi4 boundary kind must be 0 (dirichlet) or 1 (periodic)");
+      T.bc = p[2] == 1.0 ? MFM_BC_PERIODIC : MFM_BC_DIRICHLET;
+      if (T.bc == MFM_BC_DIRICHLET) {
+        if (!std::isfinite(p[3])) return fail(MFM_EINVAL, "phi4 Dirichlet boundary value must be finite");
+        T.bval = (float)p[3];
+      }
+    }
   } else if (kind == MFM_GMM) {
     const int K = (int)p[0];
     if (K <= 0 || K > MFM_GMM_MAX_MODES || np != (size_t)(1 + 2 * K * d + K)) return fail(MFM_EINVAL, "bad GMM parameter block");

@@ -95,11 +95,13 @@ __device__ __forceinline__ void store_packed(float* base, int tile_row, int nbb,
   __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(base) + ((size_t)tile_row * nbb + bb) * 64 + lane);
 }
 
-// grad log pi(x)[row][col], clipped, for the tile whose positions sit in LDS `xrow0` (row stride ldx, data at +4)
+// grad log pi(x)[row][col], clipped, for the tile whose positions sit in LDS `xrow0` (row stride ldx, data at +4).
+// BCRT: the phi-four boundary of n.T at run time (targets.hip.h: phi4_grad_bc); otherwise Dirichlet 0 through the zero pads.
+template <bool BCRT = false>
 __device__ __forceinline__ float target_gclip(const NetDev& n, const float* xbuf, int ldx, const float* gcs, const float* gcl, int ldg,
                                               int row, int col) {
   float gv;
-  if (n.T.kind == MFM_TARGET_PHI4) gv = phi4_grad(n.T, xbuf + row * ldx + 4, col);
+  if (n.T.kind == MFM_TARGET_PHI4) gv = BCRT ? phi4_grad_bc(n.T, xbuf + row * ldx + 4, col, n.d) : phi4_grad(n.T, xbuf + row * ldx + 4, col);
   else if (n.T.kind == MFM_TARGET_LGCP) gv = gcl[row * ldg + col];
   else gv = gcs[row * 8 + col];
   return clipf(gv, n.grad_clip);
@@ -116,7 +118,9 @@ __device__ __forceinline__ float target_gclip(const NetDev& n, const float* xbuf
 // log-density and prefetched uniforms of the chains): scalar arguments at the head of the list are preloaded into SGPRs (-amdgpu-kernarg-preload-count,
 // mfm_amd/build.py), so the first loads of the prologue -- the weight prefetch and the MALA step's -- go out before the read of the
 // 850-byte argument struct has returned.
-template <int TPW, bool TRAIN, bool STATIC = false, int ACT = -1, bool MALA = false>      // ACT >= 0: the activation as a compile-time constant (the five-way
+// BCRT: a phi-four boundary other than Dirichlet 0 (TargetDev::bc / ::bval, read at run time); the default instances (false) keep
+// the zero-pad stencil and are unchanged.
+template <int TPW, bool TRAIN, bool STATIC = false, int ACT = -1, bool MALA = false, bool BCRT = false>      // ACT >= 0: the activation as a compile-time constant (the five-way
 __global__ __launch_bounds__((MLP_WAVES_FM * 64)) void fm_fwd_bwd_kernel(const float* pl_w0, const float* pl_pos, const float* pl_grad, const draw_t* pl_pren,
                                                                          const double* pl_logp, const double* pl_preu, FmArgs a) {      // run-time selection in every epilogue triples the code)
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -262,7 +266,7 @@ __global__ __launch_bounds__((MLP_WAVES_FM * 64)) void fm_fwd_bwd_kernel(const f
     float* const xs[2] = {bDV + wave * L.lddv + 4, bDV + (wave + 8) * L.lddv + 4};
     float* const gsm[2] = {gcs + wave * 8, gcs + (wave + 8) * 8};
     FM_STAMP(6);
-    mala_chain_step<2 * TPW, 2>(m, bs, xs, gsm, lane, early_work);
+    mala_chain_step<2 * TPW, 2, decltype(early_work), BCRT>(m, bs, xs, gsm, lane, early_work);
     FM_STAMP(7);
   }
   __syncthreads();
@@ -409,7 +413,7 @@ __global__ __launch_bounds__((MLP_WAVES_FM * 64)) void fm_fwd_bwd_kernel(const f
                      for (int i = 0; i < 4; ++i) {
                        const int row = 4 * g + i;
                        if (col < d) {
-                         const float gc = target_gclip(n, bX, L.ldx, gcs, bGC, L.ldg, row, col);
+                         const float gc = target_gclip<BCRT>(n, bX, L.ldx, gcs, bGC, L.ldg, row, col);
                          const float v = acc[i] + bias + bG[row * L.ldg + col] * gc;
                          // tgt is indexed by the static slot q: select without dynamic register indexing
                          float tg = 0.f;
@@ -561,7 +565,7 @@ __host__ __device__ inline FmEvalLds fm_eval_lds_layout(const NetDev& n, int R =
 // (137 KB of LDS).  MT = 2: half the LDS and <= 128 registers, so TWO workgroups share a CU and one's batch construction
 // (threefry + erfinv draws, sincos, the mixture's gradient: 15 % of a workgroup's cycles, all vector ALU), epilogues and
 // barriers run under the other's MFMAs -- the measured section stamps of the MT = 4 kernel put its matrix pipe at 52 %.
-template <int MT, int ACT, bool CHAIN = false>       // ACT: the hidden non-linearity as a compile-time constant (MFM_ACT_*), or -1: read from the network
+template <int MT, int ACT, bool CHAIN = false, bool BCRT = false>       // ACT: the hidden non-linearity as a compile-time constant (MFM_ACT_*), or -1: read from the network; BCRT: as fm_fwd_bwd_kernel
 __global__ __launch_bounds__((MLP_WAVES_FM * 64), (MT == 2 ? 4 : 2)) void fm_eval_kernel(FmArgs a) {      // (threads, waves per SIMD)
   constexpr int R = 16 * MT;
   const int act = ACT >= 0 ? ACT : a.net.act;
@@ -768,7 +772,7 @@ __global__ __launch_bounds__((MLP_WAVES_FM * 64), (MT == 2 ? 4 : 2)) void fm_eva
     for (int i = 0; i < 4; ++i) {
       const int row = 16 * mt + 4 * g + i;
       if (col < d && b0 + row < a.B) {
-        const float gc = target_gclip(n, bX, L.ldx, gcs, nullptr, 0, row, col);
+        const float gc = target_gclip<BCRT>(n, bX, L.ldx, gcs, nullptr, 0, row, col);
         const float r = acc[i] + bias + bG[row * L.ldg + col] * gc - bT[row * n.dp + col];
         loss_loc += r * r;
       }
@@ -1027,6 +1031,16 @@ int launch_fm(const FmArgs& a, bool train, hipStream_t stream) {
     a2.stagger_cycles = g_sw.eval_stagger;       // measured: 1.023 -> 0.994 ms on 409,600 samples (any delay of 20 k .. 70 k cycles)
     const FmArgs& a = a2;
     const bool relu = a.net.act == MFM_ACT_RELU;
+    if (a.net.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.net.T)) {      // other phi-four boundaries: the run-time activation instances
+      if (r == 32) {
+        (void)hipFuncSetAttribute((const void*)fm_eval_kernel<2, -1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
+        hipLaunchKernelGGL((fm_eval_kernel<2, -1, false, true>), dim3((a.B + 31) / 32), dim3(MLP_WAVES_FM * 64), smr, stream, a);
+      } else {
+        (void)hipFuncSetAttribute((const void*)fm_eval_kernel<4, -1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
+        hipLaunchKernelGGL((fm_eval_kernel<4, -1, false, true>), dim3((a.B + 63) / 64), dim3(MLP_WAVES_FM * 64), smr, stream, a);
+      }
+      return 0;
+    }
     // the 32-sample relu instance with its five full-width layers chained (0.997 -> 0.985 ms on 409,600 samples; same arithmetic)
     bool chain = a.net.d == 2 && a.net.dp == 16 && !g_sw.eval_no_chain;
     for (int l : {0, 1, 3, 5, 6}) chain &= a.net.L[l].Kp % 128 == 0 && a.net.L[l].Np == 16 * MLP_WAVES_FM;
@@ -1055,6 +1069,11 @@ int launch_fm(const FmArgs& a, bool train, hipStream_t stream) {
     (void)hipFuncSetAttribute((const void*)fm_fwd_bwd_kernel<T, true, STATIC_, ACT_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
     hipLaunchKernelGGL((fm_fwd_bwd_kernel<T, true, STATIC_, ACT_, true>), grid, block, sm, stream, a.net.Wp + a.net.L[0].w_off, a.pos, a.mala.grad, a.mala.pre_n, a.mala.logp, a.mala.pre_u, a);    \
   } while (0)
+#define FM_LAUNCH_B(T, TR, STATIC_, ACT_, MALA_)                                                           \
+  do {                                                                                                     \
+    (void)hipFuncSetAttribute((const void*)fm_fwd_bwd_kernel<T, TR, STATIC_, ACT_, MALA_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
+    hipLaunchKernelGGL((fm_fwd_bwd_kernel<T, TR, STATIC_, ACT_, MALA_, true>), grid, block, sm, stream, a.net.Wp + a.net.L[0].w_off, a.pos, a.mala.grad, a.mala.pre_n, a.mala.logp, a.mala.pre_u, a); \
+  } while (0)
   const NetDev& n = a.net;
   bool headline = n.d == 256 && n.dp == 256 && n.F == 128 && n.F2p == 256 && n.ht1 == 128 && n.ht2 == 128 && n.hx1 == 128 &&
                   n.hx2 == 128 && n.hj1 == 128 && n.hj2 == 128 && n.T.kind == MFM_TARGET_PHI4 && n.act == MFM_ACT_RELU && !g_sw.generic_fm;
@@ -1065,7 +1084,18 @@ int launch_fm(const FmArgs& a, bool train, hipStream_t stream) {
     (void)hipFuncSetAttribute((const void*)fm_fwd_bwd_kernel<2, TR, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
     hipLaunchKernelGGL((fm_fwd_bwd_kernel<2, TR, true>), grid, block, sm, stream, a.net.Wp + a.net.L[0].w_off, a.pos, a.mala.grad, a.mala.pre_n, a.mala.logp, a.mala.pre_u, a);                     \
   } while (0)
-  if (a.mala.on) {      // the iteration's MALA step in the same launch (callers ask fm_mala_fusable first)
+  if (n.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.T)) {      // other phi-four boundaries: the BCRT instances, same choice
+    if (a.mala.on) {
+      if (!train || !fm_mala_fusable(n)) return -3;
+      if (headline) FM_LAUNCH_B(2, true, true, -1, true); else if (tpw <= 1) FM_LAUNCH_B(1, true, false, MFM_ACT_RELU, true); else FM_LAUNCH_B(2, true, false, MFM_ACT_RELU, true);
+    } else if (headline) {
+      if (train) FM_LAUNCH_B(2, true, true, -1, false); else FM_LAUNCH_B(2, false, true, -1, false);
+    } else if (tpw <= 1) {
+      if (train) FM_LAUNCH_B(1, true, false, -1, false); else FM_LAUNCH_B(1, false, false, -1, false);
+    } else if (tpw <= 2) {
+      if (train) FM_LAUNCH_B(2, true, false, -1, false); else FM_LAUNCH_B(2, false, false, -1, false);
+    } else return -3;
+  } else if (a.mala.on) {      // the iteration's MALA step in the same launch (callers ask fm_mala_fusable first)
     if (!train || !fm_mala_fusable(n)) return -3;
     if (headline) FM_LAUNCH_M(2, true, -1); else if (tpw <= 1) FM_LAUNCH_M(1, false, MFM_ACT_RELU); else FM_LAUNCH_M(2, false, MFM_ACT_RELU);
   } else if (headline) {
@@ -1076,6 +1106,7 @@ int launch_fm(const FmArgs& a, bool train, hipStream_t stream) {
     if (tpw <= 1) FM_LAUNCH(1, false); else if (tpw <= 2) FM_LAUNCH(2, false); else return -3;
   }
 #undef FM_LAUNCH_S
+#undef FM_LAUNCH_B
 #undef FM_LAUNCH_M
 #undef FM_LAUNCH
 #undef FM_LAUNCH_A

@@ -20,7 +20,7 @@ struct HmcArgs {
   float* acc_prob; uint8_t* accepted;                 // info (may be null)
 };
 
-template <int MAXIT>
+template <int MAXIT, bool BCRT = false>      // BCRT: as mala.hip's row kernels
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
 #pragma clang fp contract(off)
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the stencil reads its neighbours' elements from this wave's row
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    lp = row_value_grad<MAXIT>(a.T, a.beta, xs, d, lane, g, gsm);
+    lp = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, g, gsm);
     __builtin_amdgcn_wave_barrier();                             // (the next drift overwrites the row)
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {

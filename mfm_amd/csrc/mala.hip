@@ -32,7 +32,9 @@ struct MalaArgs {
 
 // value (float64, wave-reduced) and gradient of the tempered target for the row staged in `xs`.
 // grad is returned per lane for elements j = lane + 64*it in gout[it].
-template <int MAXIT>
+// BCRT: a phi-four boundary other than Dirichlet 0 (TargetDev::bc / ::bval, by index: targets.hip.h); the default instances keep
+// the zero-pad stencil (and their registers: read at run time, the boundary fields cost these kernels SGPRs and HMC a wave)
+template <int MAXIT, bool BCRT = false>
 __device__ __forceinline__ double row_value_grad(const TargetDev& T, double beta, const float* xs, int d, int lane,
                                                  float (&gout)[MAXIT], float* gsm) {
   double acc = 0.0;
@@ -41,8 +43,13 @@ __device__ __forceinline__ double row_value_grad(const TargetDev& T, double beta
     for (int it = 0; it < MAXIT; ++it) {
       int j = lane + 64 * it;
       if (j < d) {
-        acc += phi4_term(T, xs, j);
-        gout[it] = (float)beta * phi4_grad(T, xs, j);
+        if constexpr (BCRT) {
+          acc += phi4_term_bc(T, xs, j, d);      // (the boundary by index, targets.hip.h: the row's pads stay zero)
+          gout[it] = (float)beta * phi4_grad_bc(T, xs, j, d);
+        } else {
+          acc += phi4_term(T, xs, j);
+          gout[it] = (float)beta * phi4_grad(T, xs, j);
+        }
       }
     }
     return beta * wave_sum(acc);
@@ -86,7 +93,7 @@ __device__ __forceinline__ double row_value_grad(const TargetDev& T, double beta
   }
 }
 
-template <int MAXIT>
+template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void mala_init_kernel(MalaArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_init_kernel(MalaArgs a) 
   __syncthreads();
   if (!live) return;
   float g[MAXIT];
-  double lp = row_value_grad<MAXIT>(a.T, a.beta, xs, d, lane, g, gsm);
+  double lp = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, g, gsm);
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
     int j = lane + 64 * it;
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_init_kernel(MalaArgs a) 
 }
 
 // loglik only (beta_fn input, exe_flow_matching.py:413,418)
-template <int MAXIT>
+template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void loglik_kernel(MalaArgs a, double* out) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -126,7 +133,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void loglik_kernel(MalaArgs a, dou
   __syncthreads();
   if (!live) return;
   float g[MAXIT];
-  double lp = row_value_grad<MAXIT>(a.T, 1.0, xs, d, lane, g, gsm);
+  double lp = row_value_grad<MAXIT, BCRT>(a.T, 1.0, xs, d, lane, g, gsm);
   if (lane == 0) out[b] = lp;
 }
 
@@ -141,7 +148,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void loglik_kernel(MalaArgs a, dou
 // system delivers ~10 B/clk/CU and the ISSUE of a load stalls behind it; issuing the caller's loads later, after the proposal, stalled
 // just as long there and was slower: tools/fm_stamps.py --loop, 8.3 k cycles for that section.)
 struct MalaNoHook { __device__ __forceinline__ void operator()() const {} };
-template <int MAXIT, int NCH, typename Hook = MalaNoHook>
+template <int MAXIT, int NCH, typename Hook = MalaNoHook, bool BCRT = false>
 __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b)[NCH], float* const (&xs)[NCH], float* const (&gsm)[NCH], int lane,
                                                 Hook after_loads = Hook()) {
   // No multiply-add contraction in this function's own arithmetic: it is instantiated in two kernels (stand-alone, and inside the
@@ -204,7 +211,7 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
   double lpn[NCH], th2[NCH];              // th2 = |x - x' - eps g'|^2
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    lpn[c] = row_value_grad<MAXIT>(a.T, a.beta, xs[c], d, lane, gn[c], gsm[c]);    // diffusions.py:32
+    lpn[c] = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs[c], d, lane, gn[c], gsm[c]);    // diffusions.py:32
     th2[c] = 0.0;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
@@ -250,7 +257,7 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
   }
 }
 
-template <int MAXIT>
+template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void mala_step_kernel(MalaArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -260,7 +267,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_step_kernel(MalaArgs a) 
   const int bs[1] = {b};
   float* const xs[1] = {smem + wave * rowlen + 1};
   float* const gsm[1] = {smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL};
-  mala_chain_step<MAXIT, 1>(a, bs, xs, gsm, lane);
+  mala_chain_step<MAXIT, 1, MalaNoHook, BCRT>(a, bs, xs, gsm, lane);
 }
 
 // ---- launchers (called from the C ABI in api.hip) ---------------------------------------------------------
@@ -271,6 +278,13 @@ static inline size_t mala_smem(int d) { return (size_t)(MALA_WAVES * (d + 2) + M
     int nit = (a.T.dim + 63) / 64;                                                           \
     dim3 grid((a.B + MALA_WAVES - 1) / MALA_WAVES), block(MALA_WAVES * 64);                  \
     size_t sm = mala_smem(a.T.dim);                                                          \
+    if (a.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.T)) {                              \
+      if (nit <= 1) hipLaunchKernelGGL((KERN<1, true>), grid, block, sm, stream, __VA_ARGS__);        \
+      else if (nit <= 4) hipLaunchKernelGGL((KERN<4, true>), grid, block, sm, stream, __VA_ARGS__);   \
+      else if (nit <= 16) hipLaunchKernelGGL((KERN<16, true>), grid, block, sm, stream, __VA_ARGS__); \
+      else if (nit <= 32) hipLaunchKernelGGL((KERN<32, true>), grid, block, sm, stream, __VA_ARGS__); \
+      else return -2;                                                                        \
+    } else                                                                                   \
     if (nit <= 1) hipLaunchKernelGGL(KERN<1>, grid, block, sm, stream, __VA_ARGS__);         \
     else if (nit <= 4) hipLaunchKernelGGL(KERN<4>, grid, block, sm, stream, __VA_ARGS__);    \
     else if (nit <= 16) hipLaunchKernelGGL(KERN<16>, grid, block, sm, stream, __VA_ARGS__);  \

@@ -227,7 +227,8 @@ struct OdeTile {
 
   // One evaluation of the augmented field at the positions in bX (value rows) and times tt[i] (this lane's rows).
   // Outputs: kv[q][i] = dx/dt for (row 4g+i, col 16(wave+4q)+c); dl[i] = d(logdet)/dt for row 4g+i (all lanes agree).
-  template <bool WANT_JZ = false>
+  // BCRT: a phi-four boundary other than Dirichlet 0 (N.T.bc / .bval, by index: targets.hip.h); false: the zero pads as before
+  template <bool WANT_JZ = false, bool BCRT = false>
   __device__ __forceinline__ void eval(const float (&tt)[4], float (&kv)[TPW][4], float (&dl)[4], int red_slot,
                                        float (*jzo)[4] = nullptr, bool reuse_time = false) {
     const NetDev& N = *n;
@@ -413,10 +414,11 @@ struct OdeTile {
                              if (col < d) {
                                if (N.T.kind == MFM_TARGET_PHI4) {
                                  const float* xr = bX() + row * L.ldx + 4;
-                                 const float graw = phi4_grad(N.T, xr, col);
+                                 const float graw = BCRT ? phi4_grad_bc(N.T, xr, col, d) : phi4_grad(N.T, xr, col);
                                  gc = clipf(graw, N.grad_clip);
                                  const bool inside = !(N.grad_clip > 0.f) || fabsf(graw) <= N.grad_clip;
-                                 if (hutch && inside) hz = phi4_hvp(N.T, xr, bZ() + row * L.ldx + 4, col);
+                                 if (hutch && inside)
+                                   hz = BCRT ? phi4_hvp_bc(N.T, xr, bZ() + row * L.ldx + 4, col, d) : phi4_hvp(N.T, xr, bZ() + row * L.ldx + 4, col);
                                } else if (N.T.kind == MFM_TARGET_LGCP) {
                                  gc = lds[L.gc + row * L.ldgc + col];
                                  hz = lds[L.hz + row * L.ldgc + col];
@@ -600,7 +602,7 @@ enum { RS_T = 0, RS_DT = 1, RS_H0 = 2, RS_D1 = 3, RS_ELL = 4, RS_KL = 5 /* ..11 
 // ONE call site of the field evaluation, driven by a small state machine (phase 0: f0, phase 1: the extra
 // evaluation of the initial-step heuristic, phases 2..7: the six Runge-Kutta stages), so the kernel carries one copy
 // of the MLP code; stage results are routed into k[.] with predicated moves (static register indices).
-template <int TPW, int NW>
+template <int TPW, int NW, bool BCRT = false>
 __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float atol, int max_attempts,
                                           float (&y)[TPW][4], float (&ell)[4], int (&natt)[4], const Replay& rp, int rp_solve, int rp_row0) {
   const NetDev& N = *T.n;
@@ -681,7 +683,7 @@ __device__ __forceinline__ void ode_solve(OdeTile<TPW, NW>& T, float rtol, float
       const unsigned long long c0_ = __builtin_amdgcn_s_memtime();
 #endif
       if (ex2) T.eval_x2(ts, kv, dl1, phase & 1, phase == 7);
-      else T.eval(ts, kv, dl1, (phase + pj) & 1, nullptr, phase == 7 || pj > 0);
+      else T.template eval<false, BCRT>(ts, kv, dl1, (phase + pj) & 1, nullptr, phase == 7 || pj > 0);
 #ifdef MFM_STAMPS
       T.cyc_eval += __builtin_amdgcn_s_memtime() - c0_; T.n_eval += 1;
 #endif
@@ -887,7 +889,7 @@ __device__ __forceinline__ void tile_init(OdeTile<TPW, NW>& T, const NetDev* n, 
   __syncthreads();
 }
 
-template <int TPW, int NW>
+template <int TPW, int NW, bool BCRT = false>
 __global__ __launch_bounds__(NW * 64) void ode_transform_kernel(OdeArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   OdeTile<TPW, NW> T;
@@ -903,7 +905,7 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_kernel(OdeArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) y[q][i] = col < d ? a.in[(size_t)(b0 + 4 * T.g + i) * d + col] : 0.f;
   }
-  ode_solve<TPW, NW>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, 0, b0);
+  ode_solve<TPW, NW, BCRT>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, 0, b0);
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
     const int col = (T.wave + NW * q) * 16 + T.c;
@@ -922,7 +924,7 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_kernel(OdeArgs a) {
 }
 
 // v(x, t) and J z for n samples (mfm_vf_apply): one field evaluation per tile.
-template <int TPW, int NW>
+template <int TPW, int NW, bool BCRT = false>
 __global__ __launch_bounds__(NW * 64) void vf_apply_kernel(NetDev net, const float* x, const float* t, const float* tan, int n,
                                                                float* v, float* jvp) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -951,7 +953,7 @@ __global__ __launch_bounds__(NW * 64) void vf_apply_kernel(NetDev net, const flo
   for (int q = 0; q < TPW; ++q)
 #pragma unroll
     for (int i = 0; i < 4; ++i) jz[q][i] = 0.f;
-  T.template eval<true>(tt, kv, dl, 0, jz);
+  T.template eval<true, BCRT>(tt, kv, dl, 0, jz);
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
     const int col = (T.wave + NW * q) * 16 + T.c;
@@ -967,7 +969,7 @@ __global__ __launch_bounds__(NW * 64) void vf_apply_kernel(NetDev net, const flo
 }
 
 #ifdef MFM_STAMPS
-template <int TPW, int NW>
+template <int TPW, int NW, bool BCRT = false>      // (BCRT: the launch macro's; the stamps measure the default instance)
 __global__ __launch_bounds__(NW * 64) void eval_stamps_kernel(NetDev net, const float* x, const float* t, const float* tan, int reps,
                                                               unsigned long long* stamps) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -1006,7 +1008,7 @@ int launch_eval_stamps(const NetDev& n, const float* x, const float* t, const fl
 #endif
 
 // One flow-based MH step per chain (random-walk in latent space :264-278, or independent :246-260).
-template <int TPW, int NW>
+template <int TPW, int NW, bool BCRT = false>
 __global__ __launch_bounds__(NW * 64) void flow_step_kernel(OdeArgs a, FlowArgs f) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   OdeTile<TPW, NW> T;
@@ -1060,7 +1062,7 @@ __global__ __launch_bounds__(NW * 64) void flow_step_kernel(OdeArgs a, FlowArgs 
     }
     fill_probe(T, ph == 0 ? a.z1 : a.z2, b0, !T.exact);       // key_hutch2 for the inverse, key_hutch1 for the forward solve
     T.sign = ph == 0 ? -1 : 1;
-    ode_solve<TPW, NW>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, ph, b0);
+    ode_solve<TPW, NW, BCRT>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, ph, b0);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (ph == 0) vol0[i] = ell[i];
@@ -1090,8 +1092,13 @@ __global__ __launch_bounds__(NW * 64) void flow_step_kernel(OdeArgs a, FlowArgs 
         gnew[q][i] = 0.f;
         if (col < d) {
           const float* xr = T.bX() + (4 * g + i) * T.L.ldx + 4;
-          part[i] += phi4_term(N.T, xr, col);
-          gnew[q][i] = (float)f.beta * phi4_grad(N.T, xr, col);
+          if constexpr (BCRT) {
+            part[i] += phi4_term_bc(N.T, xr, col, d);
+            gnew[q][i] = (float)f.beta * phi4_grad_bc(N.T, xr, col, d);
+          } else {
+            part[i] += phi4_term(N.T, xr, col);
+            gnew[q][i] = (float)f.beta * phi4_grad(N.T, xr, col);
+          }
         }
       }
     }
@@ -1233,10 +1240,16 @@ static int ode_check(const NetDev& n, size_t& sm, int& tpw) {
   if (sm > 160 * 1024 || tpw > 2 * (8 / ODE_NW) || n.hx1 > 16 * 2 * ODE_NW) return -3;
   return 0;
 }
+// (a phi-four boundary other than Dirichlet 0: the BCRT instances; `bcrt` is in scope at every launch)
 #define ODE_LAUNCH_T(KERN, T, GRID, ...)                                                                               \
   do {                                                                                                                 \
-    (void)hipFuncSetAttribute((const void*)KERN<T, ODE_NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);      \
-    hipLaunchKernelGGL((KERN<T, ODE_NW>), GRID, dim3(ODE_NW * 64), sm, stream, __VA_ARGS__);                           \
+    if (bcrt) {                                                                                                        \
+      (void)hipFuncSetAttribute((const void*)KERN<T, ODE_NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); \
+      hipLaunchKernelGGL((KERN<T, ODE_NW, true>), GRID, dim3(ODE_NW * 64), sm, stream, __VA_ARGS__);                   \
+    } else {                                                                                                           \
+      (void)hipFuncSetAttribute((const void*)KERN<T, ODE_NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);    \
+      hipLaunchKernelGGL((KERN<T, ODE_NW>), GRID, dim3(ODE_NW * 64), sm, stream, __VA_ARGS__);                         \
+    }                                                                                                                  \
   } while (0)
 #if ODE_NW == 8
 #define ODE_LAUNCH(KERN, GRID, ...)                                                                                    \
@@ -1259,12 +1272,14 @@ int launch_ode_transform(const OdeArgs& a, hipStream_t stream) {
   if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_transform(a, stream);
   if (fast::shape_ok(a.net, a.hutch) && !g_sw.generic_ode)
     return fast::tile_width(a.net) == 256 ? fast::launch_transform_t<256>(a, a.fast_scr, stream) : fast::launch_transform_t<128>(a, a.fast_scr, stream);
+  const bool bcrt = a.net.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.net.T);
   ODE_LAUNCH(ode_transform_kernel, dim3(a.n / 16), a);
   return 0;
 }
 int launch_vf_apply(const NetDev& n, const float* x, const float* t, const float* tan, int cnt, float* v, float* jvp, hipStream_t stream) {
   size_t sm; int tpw;
   if (ode_check(n, sm, tpw)) return -3;
+  const bool bcrt = n.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.T);
   ODE_LAUNCH(vf_apply_kernel, dim3(cnt / 16), n, x, t, tan, cnt, v, jvp);
   return 0;
 }
@@ -1285,6 +1300,7 @@ int launch_flow_step(const OdeArgs& a, const FlowArgs& f, const NoiseArgs& nz, h
   if (d2::use_for(a.net, a.hutch, a.n)) return d2::launch_flow(a, f, stream);
   if (fast::shape_ok(a.net, a.hutch) && !g_sw.generic_ode)
     return fast::tile_width(a.net) == 256 ? fast::launch_flow_t<256>(a, f, nz, a.fast_scr, stream) : fast::launch_flow_t<128>(a, f, nz, a.fast_scr, stream);
+  const bool bcrt = a.net.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.net.T);
   ODE_LAUNCH(flow_step_kernel, dim3(a.n / 16), a, f);
   return 0;
 }
@@ -1293,6 +1309,7 @@ int launch_flow_step(const OdeArgs& a, const FlowArgs& f, const NoiseArgs& nz, h
 int launch_eval_stamps(const NetDev& n, const float* x, const float* t, const float* tan, int cnt, int reps, unsigned long long* stamps, hipStream_t stream) {
   size_t sm; int tpw;
   if (ode_check(n, sm, tpw)) return -3;
+  const bool bcrt = false;
   ODE_LAUNCH(eval_stamps_kernel, dim3(cnt / 16), n, x, t, tan, reps, stamps);
   return 0;
 }

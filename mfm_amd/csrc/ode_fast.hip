@@ -214,6 +214,11 @@ enum { RM_INIT0 = 0, RM_INIT1 = 1, RM_ATT = 2, RM_DONE = 3 };
 #define TAIL_PASSES 2         // a tile enters the tail with <= 2 TAIL_PASSES live rows (1: the round-3 two-row tail)
 #endif
 
+// The phi-four boundary of a PHI4_BCRT instance, handed to FTile::eval / eval_c beside the tile (NOT a member: members of the tile
+// change the register allocation of the PHI4_BC0 kernels; an unused argument of an inlined call does not)
+struct Phi4Bc { int bc = MFM_BC_DIRICHLET, d = 0; float bval = 0.f; };
+__device__ __forceinline__ Phi4Bc phi4_bc_of(const NetDev& n) { Phi4Bc p; p.bc = n.T.bc; p.d = n.d; p.bval = n.T.bval; return p; }
+
 template <int D>
 struct FTile {
   using S = FS<D>;
@@ -476,8 +481,10 @@ struct FTile {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(sr, vo, (wave * 3 + q) * 1024, 0));
   }
 
+  // BC = PHI4_BCRT: the target terms take the boundary `pb` (targets.hip.h: phi4_nb); PHI4_BC0: the zero pads, `pb` unused
+  template <int BC = PHI4_BC0>
   __device__ __forceinline__ void eval(int slot, int cur, int dst, bool next_is_tbatch, f32x4 (&P)[4], f32x4 (&Q)[4], float (&kv)[TPW][4],
-                                       const f32x4 sg, int rps = 0, const f32x4 rk = f32x4{0.f, 0.f, 0.f, 0.f}) {
+                                       const f32x4 sg, int rps = 0, const f32x4 rk = f32x4{0.f, 0.f, 0.f, 0.f}, const Phi4Bc& pb = Phi4Bc{}) {
     const bool compact = rps != 0;
 #ifdef MFM_STAMPS
     sec_t0 = __builtin_amdgcn_s_memtime();
@@ -510,8 +517,14 @@ struct FTile {
       const float* xr = at(o_xo + xsel, i * LDX + 128 * q);
       const float* zr = at(o_xo, S::ZB + i * LDX + 128 * q);
       const float x = xr[0], z = zr[0];
-      const float graw = -tbeta * (coef * (2.f * x - xr[-1] - xr[1]) - x * (1.f - x * x) * icoef);
-      const float hv = -tbeta * (coef * (2.f * z - zr[-1] - zr[1]) - (1.f - 3.f * x * x) * z * icoef);
+      float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+      if constexpr (BC == PHI4_BCRT) {
+        const int col = 16 * wave + c + 128 * q;
+        phi4_nb(pb.bc, pb.bval, xr, col, pb.d, xl, xp);
+        phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, zl, zp);
+      }
+      const float graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+      const float hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
       gc[q][i] = clip > 0.f ? fminf(fmaxf(graw, -clip), clip) : graw;
       hz[q][i] = (!(clip > 0.f) || fabsf(graw) <= clip) ? hv : 0.f;
       zz[q][i] = z;
@@ -550,6 +563,12 @@ struct FTile {
             const float* xr = at(o_xo + xsel, (i0 + e) * LDX + 128 * q);
             const float* zr = at(o_xo, S::ZB + (i0 + e) * LDX + 128 * q);
             o[0][e] = xr[0]; o[1][e] = xr[-1]; o[2][e] = xr[1]; o[3][e] = zr[0]; o[4][e] = zr[-1]; o[5][e] = zr[1];
+            if constexpr (BC == PHI4_BCRT) {
+              const int col = 16 * wave + c + 128 * q;
+              float l, r;
+              phi4_nb(pb.bc, pb.bval, xr, col, pb.d, l, r); o[1][e] = l; o[2][e] = r;
+              phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, l, r); o[4][e] = l; o[5][e] = r;
+            }
           }
         };
         // two elements per instruction (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32): beside MFMAs every vector instruction costs
@@ -715,8 +734,9 @@ struct FTile {
   // wave halves with one v_permlane32_swap per element.  Inputs: X[cur] rows 0..7 = stage inputs by rank, rows 8..15 = the
   // probes by rank (written by the owners: solve2).  The first x layer recomputes z W_x1 as its rows 8..15.  Results go
   // back to the lanes that own the chain rows (Runge-Kutta registers) through rows 0..7 of the OTHER X buffer.
+  template <int BC = PHI4_BC0>      // as eval
   __device__ __forceinline__ void eval_c(int slot, int cur, int dst, bool next_is_tbatch, f32x4 (&P)[4], f32x4 (&Q)[4], float (&kv)[TPW][4],
-                                         const f32x4 sg, int rps, const f32x4 rk) {
+                                         const f32x4 sg, int rps, const f32x4 rk, const Phi4Bc& pb = Phi4Bc{}) {
 #ifdef MFM_STAMPS
     sec_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -741,8 +761,14 @@ struct FTile {
           const float* xr = at(o_xc + xsel, (jr0 + i) * LDX + 128 * q);
           const float* zr = xr + 8 * LDX;
           const float x = xr[0], z = zr[0];
-          const float graw = -tbeta * (coef * (2.f * x - xr[-1] - xr[1]) - x * (1.f - x * x) * icoef);
-          const float hv = -tbeta * (coef * (2.f * z - zr[-1] - zr[1]) - (1.f - 3.f * x * x) * z * icoef);
+          float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+          if constexpr (BC == PHI4_BCRT) {
+            const int col = 16 * wave + c + 128 * q;
+            phi4_nb(pb.bc, pb.bval, xr, col, pb.d, xl, xp);
+            phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, zl, zp);
+          }
+          const float graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+          const float hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
           gc[q][i] = clip > 0.f ? fminf(fmaxf(graw, -clip), clip) : graw;
           hz[q][i] = (!(clip > 0.f) || fabsf(graw) <= clip) ? hv : 0.f;
           zz[q][i] = z;
@@ -852,9 +878,9 @@ struct FTile {
 // Integrate the augmented ODE from t = 0 to 1 (see ode_solve in ode.hip: same state machine, same controller).
 // Requires: Z filled (probe), halo pads of X0 / X1 / Z zero, biases in LDS.
 // RP: the parity-instrumentation instance (Replay, ode.hip); the production instance (RP = false) carries none of it.
-template <int D, bool RP>
+template <int D, bool RP, int BC = PHI4_BC0>
 __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int max_attempts, float (&y)[FTile<D>::TPW][4],
-                                      float (&ell)[4], int (&natt)[4], const Replay& rp, int rp_row0, int d_true = D) {
+                                      float (&ell)[4], int (&natt)[4], const Replay& rp, int rp_row0, int d_true = D, const Phi4Bc& pb = Phi4Bc{}) {
   using S = FS<D>;
   constexpr int TPW = FTile<D>::TPW, LDX = S::LDX;
   const int g = T.g, c = T.c, wave = T.wave;
@@ -913,8 +939,8 @@ __device__ __forceinline__ void solve(FTile<D>& T, float rtol, float atol, int m
 #endif
     float kv[TPW][4];
     const int dst = phase == 0 ? 0 : phase - 1 + (phase == 1 ? 1 : 0);
-    T.eval(phase < 2 ? 0 : (phase == 7 ? 4 : phase - 2), cur, dst, phase == 7 || phase < 2, P, Q, kv,
-           f32x4{(float)T.sign, (float)T.sign, (float)T.sign, (float)T.sign});
+    T.template eval<BC>(phase < 2 ? 0 : (phase == 7 ? 4 : phase - 2), cur, dst, phase == 7 || phase < 2, P, Q, kv,
+                        f32x4{(float)T.sign, (float)T.sign, (float)T.sign, (float)T.sign}, 0, f32x4{0.f, 0.f, 0.f, 0.f}, pb);
 #ifdef MFM_STAMPS
     T.cyc_eval += __builtin_amdgcn_s_memtime() - c1_; T.n_eval += 1;
 #endif
@@ -1280,10 +1306,14 @@ struct TailArgs {
   Replay rp;
 };
 __device__ __forceinline__ int true_dim(const TailArgs& a) { return a.d_true; }
+// with the phi-four boundary of a PHI4_BCRT instance; the PHI4_BC0 instances take TailArgs itself (a derived type, even an empty one,
+// is passed differently to the non-inlined tail and changed the main loop's allocation)
+struct TailArgsBC : TailArgs { int bc; float bval; };
+template <int BC> using TailArgsT = typename std::conditional<BC == PHI4_BC0, TailArgs, TailArgsBC>::type;
 // NOT inlined: inlined into solve2, the three loops changed the register allocation of the MAIN loop (its Runge-Kutta stages went
 // to scratch: 50 -> 63 ms).  As functions they get an allocation of their own and the main loop keeps the one it had.
-template <int D, bool RP, int P, bool PAD>
-__device__ __noinline__ void solve2_tail(TailArgs a, int b0) {
+template <int D, bool RP, int P, bool PAD, int BC = PHI4_BC0>
+__device__ __noinline__ void solve2_tail(TailArgsT<BC> a, int b0) {
   using S = FS<D>;
   using M = TailMap<D, P>;
   // The workgroup's LDS and the weight descriptor are formed HERE: as arguments they arrive as a flat pointer (every LDS address
@@ -1530,8 +1560,14 @@ __device__ __noinline__ void solve2_tail(TailArgs a, int b0) {
               const float* xr = X + (4 * p + sl2) * LDX + 4 + colw + 128 * q;
               const float* zr = xr + 2 * LDX;
               const float x = xr[0], z = zr[0];
-              const float graw = -t_beta * (t_coef * (2.f * x - xr[-1] - xr[1]) - x * (1.f - x * x) * icoef);
-              const float hv = -t_beta * (t_coef * (2.f * z - zr[-1] - zr[1]) - (1.f - 3.f * x * x) * z * icoef);
+              float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+              if constexpr (BC == PHI4_BCRT) {
+                const int col = colw + 128 * q;
+                phi4_nb(a.bc, a.bval, xr, col, a.d_true, xl, xp);
+                phi4_nb<true>(a.bc, a.bval, zr, col, a.d_true, zl, zp);
+              }
+              const float graw = -t_beta * (t_coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+              const float hv = -t_beta * (t_coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
               gc[p][q] = t_clip > 0.f ? fminf(fmaxf(graw, -t_clip), t_clip) : graw;
               hz[p][q] = (!(t_clip > 0.f) || fabsf(graw) <= t_clip) ? hv : 0.f;
               zz[p][q] = z;
@@ -1790,9 +1826,10 @@ __device__ __noinline__ void solve2_tail(TailArgs a, int b0) {
 // INIT1 with dt = h0 and unit stage coefficients in slot 0 (the extra evaluation at t0 + h0); their remaining slots are
 // ignored.  Per-row arithmetic (controller, interpolation, step sizes) is that of solve() bit for bit.
 // On return: y = proposal x' at t = 1 of the forward solve, row state holds ell (forward), vol0 (inverse), lq, counts.
-template <int D, bool RP, bool PAD>
+template <int D, bool RP, bool PAD, int BC = PHI4_BC0>
 __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const FlowArgs& f, int b0, float (&y)[FTile<D>::TPW][4], int live, int fmode) {
   using S = FS<D>;
+  [[maybe_unused]] const Phi4Bc pb = BC == PHI4_BCRT ? phi4_bc_of(a.net) : Phi4Bc{};
   constexpr int TPW = FTile<D>::TPW, LDX = S::LDX;
   const int g = T.g, c = T.c, wave = T.wave;
   const float rtol = a.rtol, atol = a.atol;
@@ -1887,8 +1924,13 @@ __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const Flow
 #ifdef MFM_STAMPS
     const unsigned long long ce0_ = __builtin_amdgcn_s_memtime();
 #endif
-    if (cmode == 0) T.eval(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), 0, rk4);
-    else T.eval_c(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), rps, rk4);
+    if constexpr (BC == PHI4_BCRT) {
+      if (cmode == 0) T.template eval<BC>(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), 0, rk4, pb);
+      else T.template eval_c<BC>(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), rps, rk4, pb);
+    } else {
+      if (cmode == 0) T.eval(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), 0, rk4);
+      else T.eval_c(phase == 7 ? 4 : phase - 2, cur, dst, phase == 7, P, Q, kv, T.rs_get(RS_SIGN), rps, rk4);
+    }
 #ifdef MFM_STAMPS
     { const unsigned long long d_ = __builtin_amdgcn_s_memtime() - ce0_;
       if (cmode == 0) { T.cyc_eval += d_; T.n_eval += 1; } else if (cmode == 3) { T.cyc_em += d_; T.n_em += 1; } else { T.cyc_ec += d_; T.n_ec += 1; } }
@@ -2025,7 +2067,8 @@ __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const Flow
 #ifdef MFM_STAMPS
       const unsigned long long tl0_ = __builtin_amdgcn_s_memtime();
 #endif
-      TailArgs ta;
+      TailArgsT<BC> ta;
+      if constexpr (BC == PHI4_BCRT) { ta.bc = a.net.T.bc; ta.bval = a.net.T.bval; }
       ta.rtol = a.rtol; ta.atol = a.atol; ta.max_attempts = a.max_attempts; ta.d_true = a.net.d;
       ta.coef = a.net.T.coef; ta.tbeta = a.net.T.tbeta; ta.clip = a.net.grad_clip; ta.fourier = a.net.fourier; ta.Wp = a.net.Wp;
       ta.zgen = a.zgen; ta.z2 = a.z2; ta.mode = fmode; ta.ref_std = f.ref_std; ta.rp = a.rp;
@@ -2033,9 +2076,9 @@ __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const Flow
       for (;;) {
         const int live = __popcll(__ballot(*T.at((T.lane & 15) * 4, S::RS + RS_RANK * 16) >= 0.f) & 0xFFFFull);
         if (live == 0) break;
-        if (TAIL_PASSES >= 3 && live > 4) solve2_tail<D, RP, TAIL_PASSES >= 3 ? 3 : 1, PAD>(ta, b0);
-        else if (TAIL_PASSES >= 2 && live > 2) solve2_tail<D, RP, TAIL_PASSES >= 2 ? 2 : 1, PAD>(ta, b0);
-        else solve2_tail<D, RP, 1, PAD>(ta, b0);
+        if (TAIL_PASSES >= 3 && live > 4) solve2_tail<D, RP, TAIL_PASSES >= 3 ? 3 : 1, PAD, BC>(ta, b0);
+        else if (TAIL_PASSES >= 2 && live > 2) solve2_tail<D, RP, TAIL_PASSES >= 2 ? 2 : 1, PAD, BC>(ta, b0);
+        else solve2_tail<D, RP, 1, PAD, BC>(ta, b0);
       }
 #ifdef MFM_STAMPS
       T.cyc_tail += __builtin_amdgcn_s_memtime() - tl0_;
@@ -2098,7 +2141,7 @@ __device__ __forceinline__ void fill_probe(FTile<D>& T, const float* z, int b0, 
   }
 }
 
-template <int D, bool RP, bool PAD = false>
+template <int D, bool RP, bool PAD = false, int BC = PHI4_BC0>
 __global__ __launch_bounds__(NW * 64) void ode_transform_fast_kernel(OdeArgs a, f32x4* scratch) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TPW = FTile<D>::TPW;
@@ -2117,7 +2160,8 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_fast_kernel(OdeArgs a, 
 #pragma unroll
       for (int i = 0; i < 4; ++i) y[q][i] = a.in[(size_t)(b0 + 4 * T.g + i) * D + col];
     }
-    solve<D, RP>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, b0, PAD ? a.net.d : D);
+    if constexpr (BC == PHI4_BCRT) solve<D, RP, BC>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, b0, PAD ? a.net.d : D, phi4_bc_of(a.net));
+    else solve<D, RP>(T, a.rtol, a.atol, a.max_attempts, y, ell, natt, a.rp, b0, PAD ? a.net.d : D);
 #pragma unroll
     for (int q = 0; q < TPW; ++q) {
       const int col = 16 * (T.wave + NW * q) + T.c;
@@ -2135,7 +2179,8 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_fast_kernel(OdeArgs a, 
 }
 
 // One flow-based MH step per chain (random-walk in latent space :264-278, or independent :246-260), PhiFour target.
-template <int D, bool RP, bool PAD = false>
+// BC: PHI4_BC0 (Dirichlet 0, the zero pads) or PHI4_BCRT (the boundary of a.net.T, targets.hip.h)
+template <int D, bool RP, bool PAD = false, int BC = PHI4_BC0>
 __global__ __launch_bounds__(NW * 64) void flow_step_fast_kernel(OdeArgs a, FlowArgs f, NoiseArgs nz, f32x4* scratch) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using S = FS<D>;
@@ -2161,7 +2206,7 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fast_kernel(OdeArgs a, Flow
     for (int i = 0; i < 4; ++i) y[q][i] = f.pos[(size_t)rsrc[i] * D + col];                          // :267 / :251
   }
   fill_probe(T, a.z1, b0, live);         // key_hutch2: probe of the inverse solve (the forward probe is loaded per row)
-  solve2<D, RP, PAD>(T, a, f, b0, y, live, fmode);    // inverse solve -> proposal -> forward solve, per row
+  solve2<D, RP, PAD, BC>(T, a, f, b0, y, live, fmode);    // inverse solve -> proposal -> forward solve, per row
   {
     const f32x4 e4 = T.rs_get(RS_ELL), v4 = T.rs_get(RS_VOL0), l4 = T.rs_get(RS_LQ), n0 = T.rs_get(RS_NTOT), n1 = T.rs_get(RS_NATT);
 #pragma unroll
@@ -2184,8 +2229,13 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fast_kernel(OdeArgs a, Flow
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float* xr = T.at(T.o_xo, S::XB0 + i * LDX + 128 * q) - col;      // row base: xr[col] is this lane's element
-        if (!PAD || col < a.net.d) part[i] += phi4_term(a.net.T, xr, col);     // (PAD: columns >= d are the zero padding of a narrower lattice)
-        gnew[q][i] = (float)f.beta * phi4_grad(a.net.T, xr, col);
+        if constexpr (BC == PHI4_BCRT) {      // (boundary by index with the true d)
+          if (!PAD || col < a.net.d) part[i] += phi4_term_bc(a.net.T, xr, col, a.net.d);
+          gnew[q][i] = (float)f.beta * phi4_grad_bc(a.net.T, xr, col, a.net.d);
+        } else {
+          if (!PAD || col < a.net.d) part[i] += phi4_term(a.net.T, xr, col);     // (PAD: columns >= d are the zero padding of a narrower lattice)
+          gnew[q][i] = (float)f.beta * phi4_grad(a.net.T, xr, col);
+        }
       }
     }
     double* rd = reinterpret_cast<double*>(lds + S::RED);      // [NW][16 rows] doubles = 2 slots
@@ -2338,10 +2388,10 @@ static bool pad_args(OdeArgs& a, hipStream_t s) {
   return true;
 }
 
-template <int D, bool RP>
+template <int D, bool RP, int BC>
 static int launch_flow_tr(const OdeArgs& a0, const FlowArgs& f0, const NoiseArgs& nz, f32x4* scratch, hipStream_t stream) {
   const size_t sm = (size_t)FS<D>::TOTAL * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)flow_step_fast_kernel<D, RP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+  (void)hipFuncSetAttribute((const void*)flow_step_fast_kernel<D, RP, false, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   OdeArgs a = a0; FlowArgs f = f0;
   const int d = a.net.d;
   if (d != D) {
@@ -2353,10 +2403,10 @@ static int launch_flow_tr(const OdeArgs& a0, const FlowArgs& f0, const NoiseArgs
   const int live = flow_live_rows(a.n);
   f.mode = (f0.mode & 0xFF) | (live == 16 ? 0 : live << 8);
   if (d != D) {
-    (void)hipFuncSetAttribute((const void*)flow_step_fast_kernel<D, RP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((flow_step_fast_kernel<D, RP, true>), dim3(a.n / live), dim3(NW * 64), sm, stream, a, f, nz, scratch);
+    (void)hipFuncSetAttribute((const void*)flow_step_fast_kernel<D, RP, true, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((flow_step_fast_kernel<D, RP, true, BC>), dim3(a.n / live), dim3(NW * 64), sm, stream, a, f, nz, scratch);
   } else {
-    hipLaunchKernelGGL((flow_step_fast_kernel<D, RP, false>), dim3(a.n / live), dim3(NW * 64), sm, stream, a, f, nz, scratch);
+    hipLaunchKernelGGL((flow_step_fast_kernel<D, RP, false, BC>), dim3(a.n / live), dim3(NW * 64), sm, stream, a, f, nz, scratch);
   }
   if (d != D) {
     unpad_rows(f.pos, f0.pos, a.n, d, D, stream); unpad_rows(f.grad, f0.grad, a.n, d, D, stream);
@@ -2366,12 +2416,14 @@ static int launch_flow_tr(const OdeArgs& a0, const FlowArgs& f0, const NoiseArgs
 }
 template <int D>
 static int launch_flow_t(const OdeArgs& a, const FlowArgs& f, const NoiseArgs& nz, f32x4* scratch, hipStream_t stream) {
-  return a.rp.dt ? launch_flow_tr<D, true>(a, f, nz, scratch, stream) : launch_flow_tr<D, false>(a, f, nz, scratch, stream);
+  if (!phi4_default_bc(a.net.T))      // any other phi-four boundary: the PHI4_BCRT instances
+    return a.rp.dt ? launch_flow_tr<D, true, PHI4_BCRT>(a, f, nz, scratch, stream) : launch_flow_tr<D, false, PHI4_BCRT>(a, f, nz, scratch, stream);
+  return a.rp.dt ? launch_flow_tr<D, true, PHI4_BC0>(a, f, nz, scratch, stream) : launch_flow_tr<D, false, PHI4_BC0>(a, f, nz, scratch, stream);
 }
-template <int D, bool RP>
+template <int D, bool RP, int BC>
 static int launch_transform_tr(const OdeArgs& a0, f32x4* scratch, hipStream_t stream) {
   const size_t sm = (size_t)FS<D>::TOTAL * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)ode_transform_fast_kernel<D, RP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+  (void)hipFuncSetAttribute((const void*)ode_transform_fast_kernel<D, RP, false, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
   OdeArgs a = a0;
   const int d = a.net.d;
   if (d != D) {
@@ -2381,17 +2433,19 @@ static int launch_transform_tr(const OdeArgs& a0, f32x4* scratch, hipStream_t st
   }
   const int tiles = a.n / 16, grid = tiles < max_wgs() ? tiles : max_wgs();
   if (d != D) {
-    (void)hipFuncSetAttribute((const void*)ode_transform_fast_kernel<D, RP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((ode_transform_fast_kernel<D, RP, true>), dim3(grid), dim3(NW * 64), sm, stream, a, scratch);
+    (void)hipFuncSetAttribute((const void*)ode_transform_fast_kernel<D, RP, true, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((ode_transform_fast_kernel<D, RP, true, BC>), dim3(grid), dim3(NW * 64), sm, stream, a, scratch);
     unpad_rows(a.out, a0.out, a.n, d, D, stream);
   } else {
-    hipLaunchKernelGGL((ode_transform_fast_kernel<D, RP, false>), dim3(grid), dim3(NW * 64), sm, stream, a, scratch);
+    hipLaunchKernelGGL((ode_transform_fast_kernel<D, RP, false, BC>), dim3(grid), dim3(NW * 64), sm, stream, a, scratch);
   }
   return 0;
 }
 template <int D>
 static int launch_transform_t(const OdeArgs& a, f32x4* scratch, hipStream_t stream) {
-  return a.rp.dt ? launch_transform_tr<D, true>(a, scratch, stream) : launch_transform_tr<D, false>(a, scratch, stream);
+  if (!phi4_default_bc(a.net.T))
+    return a.rp.dt ? launch_transform_tr<D, true, PHI4_BCRT>(a, scratch, stream) : launch_transform_tr<D, false, PHI4_BCRT>(a, scratch, stream);
+  return a.rp.dt ? launch_transform_tr<D, true, PHI4_BC0>(a, scratch, stream) : launch_transform_tr<D, false, PHI4_BC0>(a, scratch, stream);
 }
 
 }  // namespace fast

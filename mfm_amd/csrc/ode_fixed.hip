@@ -13,8 +13,8 @@
 // d = 2 four-chain tiles: wide.hip / ode_d2.hip: solve_fixed.
 namespace fast {
 
-template <int D, int METHOD>
-__device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[FTile<D>::TPW][4], float (&ell)[4]) {
+template <int D, int METHOD, int BC = PHI4_BC0>      // BC, pb: the phi-four boundary (FTile::eval)
+__device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[FTile<D>::TPW][4], float (&ell)[4], const Phi4Bc& pb = Phi4Bc{}) {
   using S = FS<D>;
   constexpr int TPW = FTile<D>::TPW, LDX = S::LDX;
   constexpr int NK = METHOD == MFM_ODE_RK4 ? 4 : 1, SPB = METHOD == MFM_ODE_RK4 ? 2 : 5;      // stages per step, steps per time batch
@@ -83,7 +83,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
       }
       float kv[TPW][4];
       if constexpr (METHOD == MFM_ODE_EULER) {
-        T.eval(ss, cur, 4 * par, last_of_batch, P, Q, kv, sg);
+        T.template eval<BC>(ss, cur, 4 * par, last_of_batch, P, Q, kv, sg, 0, f32x4{0.f, 0.f, 0.f, 0.f}, pb);
         cur ^= 1;
 #pragma unroll
         for (int q = 0; q < TPW; ++q)
@@ -103,7 +103,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
             write_x(x);
             __syncthreads();
           }
-          T.eval(2 * ss + (j == 0 ? 0 : (j == 3 ? 2 : 1)), cur, 4 * par + j, last_of_batch && j == 3, P, Q, kv, sg);
+          T.template eval<BC>(2 * ss + (j == 0 ? 0 : (j == 3 ? 2 : 1)), cur, 4 * par + j, last_of_batch && j == 3, P, Q, kv, sg, 0, f32x4{0.f, 0.f, 0.f, 0.f}, pb);
           cur ^= 1;
 #pragma unroll
           for (int q = 0; q < TPW; ++q)
@@ -126,7 +126,7 @@ __device__ __forceinline__ void solve_fixed(FTile<D>& T, int nsteps, float (&y)[
 }
 
 // CNF transform / inverse with log-det on N fixed steps (exe_flow_matching.py:206-242 with the integrator swapped)
-template <int D, int METHOD, bool PAD = false>
+template <int D, int METHOD, bool PAD = false, int BC = PHI4_BC0>      // BC: as flow_step_fast_kernel
 __global__ __launch_bounds__(NW * 64) void ode_transform_fixed_kernel(OdeArgs a, int nsteps, f32x4* scratch) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TPW = FTile<D>::TPW;
@@ -145,7 +145,8 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_fixed_kernel(OdeArgs a,
 #pragma unroll
       for (int i = 0; i < 4; ++i) y[q][i] = a.in[(size_t)(b0 + 4 * T.g + i) * D + col];
     }
-    solve_fixed<D, METHOD>(T, nsteps, y, ell);
+    if constexpr (BC == PHI4_BCRT) solve_fixed<D, METHOD, BC>(T, nsteps, y, ell, phi4_bc_of(a.net));
+    else solve_fixed<D, METHOD>(T, nsteps, y, ell);
 #pragma unroll
     for (int q = 0; q < TPW; ++q) {
       const int col = 16 * (T.wave + NW * q) + T.c;
@@ -165,7 +166,7 @@ __global__ __launch_bounds__(NW * 64) void ode_transform_fixed_kernel(OdeArgs a,
 // One random-walk flow-MH step per chain (exe_flow_matching.py:264-278) with both solves on N fixed steps: inverse solve ->
 // latent proposal -> forward solve, tile-wide (every row is in the same phase), then the target at the proposal and the accept
 // step exactly as flow_step_fast_kernel.
-template <int D, int METHOD, bool PAD = false>
+template <int D, int METHOD, bool PAD = false, int BC = PHI4_BC0>
 __global__ __launch_bounds__(NW * 64) void flow_step_fixed_kernel(OdeArgs a, FlowArgs f, int nsteps, f32x4* scratch) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   using S = FS<D>;
@@ -182,7 +183,8 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fixed_kernel(OdeArgs a, Flo
   }
   fill_probe(T, a.z1, b0);                 // key_hutch2
   T.sign = -1;
-  solve_fixed<D, METHOD>(T, nsteps, y, vol0);                                                      // :267 inverse_and_logdet
+  if constexpr (BC == PHI4_BCRT) solve_fixed<D, METHOD, BC>(T, nsteps, y, vol0, phi4_bc_of(a.net));
+  else solve_fixed<D, METHOD>(T, nsteps, y, vol0);                                                      // :267 inverse_and_logdet
   const float scale = 2.38f / sqrtf((float)(PAD ? a.net.d : D));                                   // :262
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
@@ -193,7 +195,8 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fixed_kernel(OdeArgs a, Flo
   __syncthreads();
   fill_probe(T, a.z2, b0);                 // key_hutch1
   T.sign = 1;
-  solve_fixed<D, METHOD>(T, nsteps, y, ell);                                                       // :269 transform_and_logdet
+  if constexpr (BC == PHI4_BCRT) solve_fixed<D, METHOD, BC>(T, nsteps, y, ell, phi4_bc_of(a.net));      // :269 transform_and_logdet
+  else solve_fixed<D, METHOD>(T, nsteps, y, ell);
   // ---- target at the proposal (:270), tempered: beta * loglik (logprior = 0) ----
   __syncthreads();
 #pragma unroll
@@ -211,8 +214,13 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fixed_kernel(OdeArgs a, Flo
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float* xr = T.at(T.o_xo, S::XB0 + i * LDX + 128 * q) - col;
-        if (!PAD || col < a.net.d) part[i] += phi4_term(a.net.T, xr, col);
-        gnew[q][i] = (float)f.beta * phi4_grad(a.net.T, xr, col);
+        if constexpr (BC == PHI4_BCRT) {
+          if (!PAD || col < a.net.d) part[i] += phi4_term_bc(a.net.T, xr, col, a.net.d);
+          gnew[q][i] = (float)f.beta * phi4_grad_bc(a.net.T, xr, col, a.net.d);
+        } else {
+          if (!PAD || col < a.net.d) part[i] += phi4_term(a.net.T, xr, col);
+          gnew[q][i] = (float)f.beta * phi4_grad(a.net.T, xr, col);
+        }
       }
     }
     double* rd = reinterpret_cast<double*>(lds + S::RED);
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(NW * 64) void flow_step_fixed_kernel(OdeArgs a, Flo
   }
 }
 
-template <int D, int METHOD>
+template <int D, int METHOD, int BC>
 static int launch_flow_fixed_m(const OdeArgs& a0, const FlowArgs& f0, int nsteps, f32x4* scratch, hipStream_t stream) {
   const size_t sm = (size_t)FS<D>::TOTAL * sizeof(float);
   OdeArgs a = a0; FlowArgs f = f0;
@@ -278,17 +286,17 @@ static int launch_flow_fixed_m(const OdeArgs& a0, const FlowArgs& f0, int nsteps
     const PadWs& w = *t_pad;
     pad_rows(f0.pos, w.img[0], a.n, d, D, stream); pad_rows(f0.grad, w.img[1], a.n, d, D, stream);
     f.pos = w.img[0]; f.grad = w.img[1]; f.proposed = f0.proposed ? w.img[2] : nullptr;
-    (void)hipFuncSetAttribute((const void*)flow_step_fixed_kernel<D, METHOD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((flow_step_fixed_kernel<D, METHOD, true>), dim3(a.n / 16), dim3(NW * 64), sm, stream, a, f, nsteps, scratch);
+    (void)hipFuncSetAttribute((const void*)flow_step_fixed_kernel<D, METHOD, true, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((flow_step_fixed_kernel<D, METHOD, true, BC>), dim3(a.n / 16), dim3(NW * 64), sm, stream, a, f, nsteps, scratch);
     unpad_rows(f.pos, f0.pos, a.n, d, D, stream); unpad_rows(f.grad, f0.grad, a.n, d, D, stream);
     if (f0.proposed) unpad_rows(f.proposed, f0.proposed, a.n, d, D, stream);
   } else {
-    (void)hipFuncSetAttribute((const void*)flow_step_fixed_kernel<D, METHOD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((flow_step_fixed_kernel<D, METHOD, false>), dim3(a.n / 16), dim3(NW * 64), sm, stream, a, f, nsteps, scratch);
+    (void)hipFuncSetAttribute((const void*)flow_step_fixed_kernel<D, METHOD, false, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((flow_step_fixed_kernel<D, METHOD, false, BC>), dim3(a.n / 16), dim3(NW * 64), sm, stream, a, f, nsteps, scratch);
   }
   return 0;
 }
-template <int D, int METHOD>
+template <int D, int METHOD, int BC>
 static int launch_transform_fixed_m(const OdeArgs& a0, int nsteps, f32x4* scratch, hipStream_t stream) {
   const size_t sm = (size_t)FS<D>::TOTAL * sizeof(float);
   OdeArgs a = a0;
@@ -298,24 +306,35 @@ static int launch_transform_fixed_m(const OdeArgs& a0, int nsteps, f32x4* scratc
     if (!pad_args<D>(a, stream)) return -3;
     pad_rows(a0.in, t_pad->img[0], a.n, d, D, stream);
     a.in = t_pad->img[0]; a.out = t_pad->img[2];
-    (void)hipFuncSetAttribute((const void*)ode_transform_fixed_kernel<D, METHOD, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((ode_transform_fixed_kernel<D, METHOD, true>), dim3(grid), dim3(NW * 64), sm, stream, a, nsteps, scratch);
+    (void)hipFuncSetAttribute((const void*)ode_transform_fixed_kernel<D, METHOD, true, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((ode_transform_fixed_kernel<D, METHOD, true, BC>), dim3(grid), dim3(NW * 64), sm, stream, a, nsteps, scratch);
     unpad_rows(a.out, a0.out, a.n, d, D, stream);
   } else {
-    (void)hipFuncSetAttribute((const void*)ode_transform_fixed_kernel<D, METHOD, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
-    hipLaunchKernelGGL((ode_transform_fixed_kernel<D, METHOD, false>), dim3(grid), dim3(NW * 64), sm, stream, a, nsteps, scratch);
+    (void)hipFuncSetAttribute((const void*)ode_transform_fixed_kernel<D, METHOD, false, BC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);
+    hipLaunchKernelGGL((ode_transform_fixed_kernel<D, METHOD, false, BC>), dim3(grid), dim3(NW * 64), sm, stream, a, nsteps, scratch);
   }
   return 0;
 }
-static int launch_flow_fixed(const OdeArgs& a, const FlowArgs& f, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
+template <int BC>
+static int launch_flow_fixed_b(const OdeArgs& a, const FlowArgs& f, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
   const bool w256 = tile_width(a.net) == 256;
-  if (method == MFM_ODE_RK4) return w256 ? launch_flow_fixed_m<256, MFM_ODE_RK4>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_RK4>(a, f, nsteps, scratch, stream);
-  return w256 ? launch_flow_fixed_m<256, MFM_ODE_EULER>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_EULER>(a, f, nsteps, scratch, stream);
+  if (method == MFM_ODE_RK4) return w256 ? launch_flow_fixed_m<256, MFM_ODE_RK4, BC>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_RK4, BC>(a, f, nsteps, scratch, stream);
+  return w256 ? launch_flow_fixed_m<256, MFM_ODE_EULER, BC>(a, f, nsteps, scratch, stream) : launch_flow_fixed_m<128, MFM_ODE_EULER, BC>(a, f, nsteps, scratch, stream);
+}
+template <int BC>
+static int launch_transform_fixed_b(const OdeArgs& a, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
+  const bool w256 = tile_width(a.net) == 256;
+  if (method == MFM_ODE_RK4) return w256 ? launch_transform_fixed_m<256, MFM_ODE_RK4, BC>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_RK4, BC>(a, nsteps, scratch, stream);
+  return w256 ? launch_transform_fixed_m<256, MFM_ODE_EULER, BC>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_EULER, BC>(a, nsteps, scratch, stream);
+}
+// Dirichlet 0: the PHI4_BC0 instances as before; any other phi-four boundary: the PHI4_BCRT ones
+static int launch_flow_fixed(const OdeArgs& a, const FlowArgs& f, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
+  return phi4_default_bc(a.net.T) ? launch_flow_fixed_b<PHI4_BC0>(a, f, method, nsteps, scratch, stream)
+                                  : launch_flow_fixed_b<PHI4_BCRT>(a, f, method, nsteps, scratch, stream);
 }
 static int launch_transform_fixed(const OdeArgs& a, int method, int nsteps, f32x4* scratch, hipStream_t stream) {
-  const bool w256 = tile_width(a.net) == 256;
-  if (method == MFM_ODE_RK4) return w256 ? launch_transform_fixed_m<256, MFM_ODE_RK4>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_RK4>(a, nsteps, scratch, stream);
-  return w256 ? launch_transform_fixed_m<256, MFM_ODE_EULER>(a, nsteps, scratch, stream) : launch_transform_fixed_m<128, MFM_ODE_EULER>(a, nsteps, scratch, stream);
+  return phi4_default_bc(a.net.T) ? launch_transform_fixed_b<PHI4_BC0>(a, method, nsteps, scratch, stream)
+                                  : launch_transform_fixed_b<PHI4_BCRT>(a, method, nsteps, scratch, stream);
 }
 
 }  // namespace fast

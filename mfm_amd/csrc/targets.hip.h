@@ -1,14 +1,23 @@
 // Target densities evaluated on the device: value, gradient and Hessian-vector product, per chain row.
-// Follows distributions.py:114-165 (PhiFour, Dirichlet b.c.), :42-77 (GaussianMixture, diagonal) and
+// Follows distributions.py:114-165 (PhiFour, Dirichlet or periodic b.c.), :42-77 (GaussianMixture, diagonal) and
 // :231-314 (LogGaussianCoxPines, unwhitened).  The reference differentiates with jax.grad / jax.jvp; these are
 // the closed forms, checked against the CPU oracle in tests/test_gpu_*.py.
 //
 // Row convention: a chain's position lives in an LDS row `xs` with one zero pad on EACH side
-// (xs[-1] = xs[d] = 0), so the PhiFour stencil needs no branches.
+// (xs[-1] = xs[d] = 0), so the Dirichlet-0 PhiFour stencil needs no branches (phi4_grad / phi4_term / phi4_hvp).
+// Other boundaries (TargetDev::bc, ::bval) take the neighbours of the two end elements BY INDEX instead
+// (phi4_nb and the *_bc forms): the x row's ends see b (Dirichlet) or the row's other end (periodic), a probe /
+// tangent row's ends see 0 (Dirichlet, any b) or its other end (periodic).  The pads are never read there, so
+// they stay zero whatever the boundary, rows of different kinds may share them, and the zero state columns
+// d .. D-1 of a narrower lattice on a wider tile are never taken for a neighbour.
 #pragma once
 #include "common.hip.h"
 
 enum { MFM_TARGET_PHI4 = 0, MFM_TARGET_GMM = 1, MFM_TARGET_LGCP = 2 };
+enum { MFM_BC_DIRICHLET = 0, MFM_BC_PERIODIC = 1 };      // PhiFour boundary (TargetDev::bc)
+// compile-time boundary of a shape-specialised / static kernel instance: PHI4_BC0 = Dirichlet 0 through the zero pads (no
+// boundary code at all), PHI4_BCRT = the boundary of TargetDev::bc / ::bval, selected at run time by index (phi4_nb)
+enum { PHI4_BC0 = 0, PHI4_BCRT = 1 };
 
 #define MFM_GMM_MAX_MODES 64
 
@@ -29,7 +38,11 @@ struct TargetDev {
   const float* kbias;      // [dp]: -mu * rowsum(K^-1), so that x . K^-1 + kbias = K^-1 (x - mu)
   const float* kdiag;      // [dp]: diag(K^-1) (the Hessian diagonal of the exact-trace log-det, wide.hip)
   float mu, poisson_a, log_norm;
+  // phi4 boundary (distributions.py:130-139): MFM_BC_DIRICHLET with both ends held at bval, or MFM_BC_PERIODIC (bval unused)
+  int bc;
+  float bval;
 };
+__host__ __device__ __forceinline__ bool phi4_default_bc(const TargetDev& T) { return T.bc == MFM_BC_DIRICHLET && T.bval == 0.f; }
 
 // ---- PhiFour --------------------------------------------------------------------------------------
 // loglik terms of element j (to be summed over j): -beta (coef/2 (x_{j+1}-x_j)^2 [+ left edge] + (1-x^2)^2/(4 coef))
@@ -53,6 +66,40 @@ __device__ __forceinline__ double phi4_term(const TargetDev& T, const float* xs,
 __device__ __forceinline__ float phi4_hvp(const TargetDev& T, const float* xs, const float* vs, int j) {
   float x = xs[j], v = vs[j];
   float lap = 2.f * v - vs[j - 1] - vs[j + 1];
+  return -T.tbeta * (T.coef * lap - (1.f - 3.f * x * x) * v / T.coef);
+}
+
+
+// The same terms for any boundary.  `p` points at element j of a row of length d (p - j = element 0); PROBE: a probe / tangent
+// row (0 beyond a Dirichlet end).  With bc = Dirichlet and bval = 0 every form rounds exactly as its pad form above.
+template <bool PROBE = false>
+__device__ __forceinline__ void phi4_nb(int bc, float bval, const float* p, int j, int d, float& l, float& r) {
+  const bool per = bc == MFM_BC_PERIODIC;
+  const float e = PROBE ? 0.f : bval;
+  l = j > 0 ? p[-1] : (per ? p[d - 1] : e);
+  r = j + 1 < d ? p[1] : (per ? p[1 - d] : e);
+}
+__device__ __forceinline__ float phi4_grad_bc(const TargetDev& T, const float* xs, int j, int d) {
+  float x = xs[j], l, r;
+  phi4_nb(T.bc, T.bval, xs + j, j, d, l, r);
+  float lap = 2.f * x - l - r;
+  return -T.tbeta * __builtin_fmaf(T.coef, lap, -(x * __builtin_fmaf(-x, x, 1.f) / T.coef));
+}
+__device__ __forceinline__ double phi4_term_bc(const TargetDev& T, const float* xs, int j, int d) {
+  // bond (j, j+1) with x_d from the boundary; the left bond (x_0 - b)^2 for j == 0 under Dirichlet only (periodic: d bonds)
+  double x = xs[j];
+  float l, r;
+  phi4_nb(T.bc, T.bval, xs + j, j, d, l, r);
+  double dr = (double)r - x;
+  double u = dr * dr;
+  if (j == 0 && T.bc != MFM_BC_PERIODIC) { const double xb = x - (double)T.bval; u = __builtin_fma(xb, xb, u); }
+  double q = __builtin_fma(-x, x, 1.0);
+  return -(double)T.tbeta * __builtin_fma(0.5 * (double)T.coef, u, q * q / (4.0 * (double)T.coef));
+}
+__device__ __forceinline__ float phi4_hvp_bc(const TargetDev& T, const float* xs, const float* vs, int j, int d) {
+  float x = xs[j], v = vs[j], l, r;
+  phi4_nb<true>(T.bc, T.bval, vs + j, j, d, l, r);
+  float lap = 2.f * v - l - r;
   return -T.tbeta * (T.coef * lap - (1.f - 3.f * x * x) * v / T.coef);
 }
 

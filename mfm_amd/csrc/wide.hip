@@ -605,6 +605,8 @@ struct TgtArgs {
   const int* cmap;          // non-null: X / KV / GC / HZ rows are COMPACT (row j = chain cmap[j]); Z / KZ stay indexed by chain
   int diag;                 // exact trace: HZ = 1[|g| <= clip] * H_ii, the DIAGONAL of the target's Hessian (Z, KZ unused)
 };
+// BCRT: a phi-four boundary other than Dirichlet 0 (targets.hip.h: phi4_nb); the default instance keeps the zero ends
+template <bool BCRT = false>
 __global__ __launch_bounds__(256) void target_kernel(TgtArgs a) {
   const size_t n = (size_t)a.rows * a.dp;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (size_t)gridDim.x * 256) {
@@ -616,11 +618,14 @@ __global__ __launch_bounds__(256) void target_kernel(TgtArgs a) {
       const float x = a.X[idx];
       float graw, hraw = 0.f;
       if (a.T.kind == MFM_TARGET_PHI4) {
-        const float xl = col > 0 ? a.X[idx - 1] : 0.f, xr = col + 1 < a.d ? a.X[idx + 1] : 0.f;
+        float xl = col > 0 ? a.X[idx - 1] : 0.f, xr = col + 1 < a.d ? a.X[idx + 1] : 0.f;
+        if constexpr (BCRT) phi4_nb(a.T.bc, a.T.bval, a.X + idx, col, a.d, xl, xr);      // (by index: Dirichlet b or periodic)
         graw = -a.T.tbeta * (a.T.coef * (2.f * x - xl - xr) - x * (1.f - x * x) / a.T.coef);
         if (a.diag) hraw = -a.T.tbeta * (a.T.coef * 2.f - (1.f - 3.f * x * x) / a.T.coef);
         else if (a.Z) {
-          const float v = a.Z[zi], vl = col > 0 ? a.Z[zi - 1] : 0.f, vr = col + 1 < a.d ? a.Z[zi + 1] : 0.f;
+          const float v = a.Z[zi];
+          float vl = col > 0 ? a.Z[zi - 1] : 0.f, vr = col + 1 < a.d ? a.Z[zi + 1] : 0.f;
+          if constexpr (BCRT) phi4_nb<true>(a.T.bc, a.T.bval, a.Z + zi, col, a.d, vl, vr);
           hraw = -a.T.tbeta * (a.T.coef * (2.f * v - vl - vr) - (1.f - 3.f * x * x) * v / a.T.coef);
         }
       } else {
@@ -1053,6 +1058,7 @@ __global__ __launch_bounds__(256) void flow_propose_kernel(FlowGlue a) {
   }
 }
 // after the forward solve: tempered target at the proposal (:270 / :252), unclipped acceptance ratio, accept / reject
+template <bool BCRT = false>      // as target_kernel
 __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.rows) return;
@@ -1063,10 +1069,15 @@ __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
     double part = 0.0;
     for (int col = lane; col < a.d; col += 64) {
       const double x = y[col];
-      const double xr = col + 1 < a.d ? (double)y[col + 1] : 0.0;
+      double xr = col + 1 < a.d ? (double)y[col + 1] : 0.0;
+      if constexpr (BCRT) if (col + 1 >= a.d) xr = a.T.bc == MFM_BC_PERIODIC ? (double)y[0] : (double)a.T.bval;
       const double dr = xr - x;
       double u = dr * dr;
-      if (col == 0) u += x * x;
+      if constexpr (BCRT) {
+        if (col == 0 && a.T.bc != MFM_BC_PERIODIC) { const double xb = x - (double)a.T.bval; u += xb * xb; }
+      } else {
+        if (col == 0) u += x * x;
+      }
       const double q = 1.0 - x * x;
       part += -(double)a.T.tbeta * (0.5 * (double)a.T.coef * u + q * q / (4.0 * (double)a.T.coef));
     }
@@ -1099,7 +1110,8 @@ __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
     if (acc) {
       float gv;
       if (a.T.kind == MFM_TARGET_PHI4) {
-        const float xl = col > 0 ? y[col - 1] : 0.f, xr = col + 1 < a.d ? y[col + 1] : 0.f;
+        float xl = col > 0 ? y[col - 1] : 0.f, xr = col + 1 < a.d ? y[col + 1] : 0.f;
+        if constexpr (BCRT) phi4_nb(a.T.bc, a.T.bval, y + col, col, a.d, xl, xr);
         gv = (float)a.beta * (-a.T.tbeta * (a.T.coef * (2.f * xv - xl - xr) - xv * (1.f - xv * xv) / a.T.coef));
       } else if (a.T.kind == MFM_TARGET_GMM) {
         gv = 0.f;
@@ -1406,7 +1418,8 @@ static void target_eval(Ctx* w, const NetDev& n, const float* X, const float* Z,
   t.diag = diag ? 1 : 0;
   t.cmap = w->cmap_use;
   if (n.T.kind == MFM_TARGET_GMM) { hipLaunchKernelGGL(target_gmm_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, t); return; }
-  hipLaunchKernelGGL(target_kernel, dim3(grid_el((size_t)rows * n.dp)), dim3(256), 0, s, t);
+  if (n.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.T)) hipLaunchKernelGGL(target_kernel<true>, dim3(grid_el((size_t)rows * n.dp)), dim3(256), 0, s, t);
+  else hipLaunchKernelGGL(target_kernel<false>, dim3(grid_el((size_t)rows * n.dp)), dim3(256), 0, s, t);
 }
 
 // time branch (exe_flow_matching.py:73-75,81): Fourier rows -> the t layers (the last one into the st half of [sx | st]) -> gate.
@@ -1910,7 +1923,8 @@ static int flow_step(Ctx* w, const NetDev& n, const FlowCall& c, hipStream_t s) 
   rc = fixed ? solve_fixed(w, n, FixedArgs{1, c.fixed_method, c.fixed_steps, rows}, w->cond, s) : solve(w, n, sa, w->cond, s);
   if (rc) return rc;
   if (n.T.kind == MFM_TARGET_LGCP) launch_gemm(kinv(n, w->Y, w->kv, rows, true), s);
-  hipLaunchKernelGGL(flow_accept_kernel, dim3(grid4(rows)), dim3(256), 0, s, f);
+  if (n.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.T)) hipLaunchKernelGGL(flow_accept_kernel<true>, dim3(grid4(rows)), dim3(256), 0, s, f);
+  else hipLaunchKernelGGL(flow_accept_kernel<false>, dim3(grid4(rows)), dim3(256), 0, s, f);
   return 0;
 }
 

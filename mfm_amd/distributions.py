@@ -106,18 +106,33 @@ class Distribution:
 
 
 class PhiFour(Distribution):
-    """``distributions.py:114-165`` (Dirichlet boundary; the ``tilt`` branch is dead in the reference)."""
+    """``distributions.py:114-165``: ``bc=('dirichlet', b)`` holds both ends at b (d + 1 bonds), ``bc=('pbc', .)`` closes the
+    lattice into a ring (d bonds; the value is ignored).  The ``tilt`` branch is dead in the reference and is not built."""
 
     kind = "phi4"
+    BC_KINDS = {"dirichlet": 0, "pbc": 1}
 
     def __init__(self, dim, a=0.1, beta=20.0, bc=("dirichlet", 0), tilt=None):
-        if bc[0] != "dirichlet" or bc[1] != 0 or tilt is not None:
-            raise NotImplementedError("only the Dirichlet-0, untilted PhiFour of multi_modal.py:53 is built")
+        if tilt is not None:
+            raise NotImplementedError("the tilted PhiFour is not built (its branch reads an undefined attribute in the reference)")
+        name, value = bc[0], bc[1]
+        if name not in self.BC_KINDS:
+            raise ValueError(f"unknown PhiFour boundary {name!r}: expected one of {sorted(self.BC_KINDS)}")
+        if name == "dirichlet":
+            value = float(value)
+            if not np.isfinite(value):
+                raise ValueError(f"the Dirichlet boundary value must be finite, got {value}")
         self.dim, self.a, self.beta = int(dim), a, beta
+        self.bc = (name, value)
         self.log_Z, self.n_plots, self.can_sample = 0.0, 0, False
 
     def target_block(self):
-        return 0, [self.a, self.beta]
+        """``[a, beta]`` for Dirichlet 0 (the block every context had before boundaries existed); otherwise
+        ``[a, beta, kind, b]`` with kind 0 = Dirichlet at b, 1 = periodic (b = 0, unused)."""
+        name, value = self.bc
+        if name == "dirichlet" and value == 0:
+            return 0, [self.a, self.beta]
+        return 0, [self.a, self.beta, float(self.BC_KINDS[name]), float(value) if name == "dirichlet" else 0.0]
 
     def initialize_model(self, rng_key, n_chain):
         keys = jr.split(rng_key, n_chain)                                   # :163

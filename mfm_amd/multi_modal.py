@@ -43,7 +43,7 @@ def main(args):
         args.lim, args.num_chain, args.eval_iter, args.step_size = [-1.6, 1.6], 1024, 1, 0.0001
         if args.force_dim:
             args.dim = args.force_dim
-        dist = PhiFour(args.dim)
+        dist = PhiFour(args.dim, bc=(getattr(args, 'phi4_bc', 'dirichlet'), getattr(args, 'phi4_bc_value', 0.0)))
         dist.sample_model = None
     elif args.example == "4-mode":                                                      # :65-85
         print("Setting up 4-mode Gaussian mixture density...")
@@ -155,6 +155,10 @@ def build_parser():
     # not in the reference -- an HMC step of --hmc_steps velocity-Verlet steps of size --step_size (mfm_amd/bblackjax/mcmc/hmc.py)
     parser.add_argument('--mcmc_kernel', type=str, default='mala', choices=['mala', 'hmc'])
     parser.add_argument('--hmc_steps', type=int, default=10)
+    # the phi-four lattice's boundary (distributions.py:114-139; the reference's main script builds Dirichlet 0): both ends held at
+    # --phi4_bc_value, or a periodic ring (--phi4_bc pbc; the value is ignored)
+    parser.add_argument('--phi4_bc', type=str, default='dirichlet', choices=['dirichlet', 'pbc'])
+    parser.add_argument('--phi4_bc_value', type=float, default=0.0)
     return parser
 
 
