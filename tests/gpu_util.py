@@ -179,3 +179,61 @@ def cached_oracle(tag, compute, *inputs):
         os.makedirs(wd, exist_ok=True)
         np.savez_compressed(os.path.join(wd, f"oracle_{tag}.npz"), input_digest=np.array(digest), **out)
     return out
+
+
+def train_like_bench(workload, n_iter=None, seed=1):
+    """The state bench.py's timed region starts from for any of its workloads (``gaussian-mixture``: configs[1], 4096 chains, K = 100,
+    exact trace; ``4-mode``: configs[0], 512 chains, K = 10, n_ts = 5; ``pines``: configs[4] per GPU, 1024 chains, hidden 1024, --hutch):
+    the flax-style initial network trained for ``n_iter`` iterations of the product's loop (default K + 1: one full cycle incl. its flow
+    step), beta = 1.  Returns the trained parameters, the chain positions and the oracle-side objects of the same configuration
+    (``args`` with the workload's chain count, ``n_ts`` and trace mode)."""
+    import sys, os
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from mfm_amd import exe_flow_matching as E, random as jr
+    from mfm_amd._lib import FLOW_RWMH
+    from mfm_amd.distributions import GaussianMixture, LogGaussianCoxPines
+    from mfm_amd.engine import Engine
+    example, dim, h, eps, chains, K = bench.WORKLOADS[workload]
+    n_iter = K + 1 if n_iter is None else n_iter
+    args = bench.make_args(chains, learning_iter=10000, workload=workload)
+    if workload == "gaussian-mixture":
+        from mfm_amd.multi_modal import gmm16_parameters
+        m, c, w = gmm16_parameters()
+        dist, o_dist = GaussianMixture(m, c, w), targets.GaussianMixture(m, c, w)
+    elif workload == "4-mode":
+        m, c, w = 8.0 * np.array([[1, 1], [1, -1], [-1, 1], [-1, -1.0]]), np.ones((4, 2)), np.ones(4) / 4
+        dist, o_dist = GaussianMixture(m, c, w), targets.GaussianMixture(m, c, w)
+    elif workload == "pines":
+        dist = LogGaussianCoxPines(dim)
+        n = int(round(np.sqrt(dim)))
+        counts = np.load(os.path.join(root, "mfm_amd", "data", "pines_counts.npz"))[f"counts_{n}"]
+        o_dist = targets.LogGaussianCoxPines(dim, counts)
+    else:
+        raise ValueError(workload)
+    key_target, key_sample, key_init, key_dist, key_fourier, key_gen = jr.split(jr.PRNGKey(seed), 6)
+    dist.initialize_model(key_dist, chains)
+    fourier = args.fourier_std * jr.normal(key_fourier, (args.fourier_dim,))
+    eng = Engine(dist, args, fourier)
+    model = E.VectorFieldNet(fourier, dist.grad_logprob, args.hidden_x, args.hidden_t, args.hidden_xt).attach(eng)
+    eng.ctx.set_params(E.flatten_params(model.init(key_init)))
+    pos = eng.local(dist.init_params)
+    logp = torch.empty(chains, device=eng.dev, dtype=torch.float64); grad = torch.empty_like(pos)
+    acc = torch.empty(chains, device=eng.dev, dtype=torch.float32); nst = torch.zeros(chains, device=eng.dev, dtype=torch.int32)
+    eng.ctx.mala_init(pos, 1.0, logp, grad)
+    ks = key_sample
+    for count in range(1, n_iter + 1):
+        ks, k_gn, k_step = jr.split(ks, 3)
+        eng.train_iter(count, K, FLOW_RWMH, k_gn, k_step, 1.0, args.step_size, pos, logp, grad, acc=acc, nsteps=nst)
+    eng.ctx.sync()
+    out = dict(params_flat=eng.ctx.get_params(), pos=pos.cpu().numpy(), fourier=np.asarray(fourier, dtype=np.float64),
+               n_att_last_flow=nst.cpu().numpy().copy())
+    eng.close()
+    oargs = loop.default_args(example=example, dim=dim, num_chain=chains, hutchs=bool(args.hutchs), step_size=eps, seed=seed,
+                              mcmc_per_flow_steps=float(K), fourier_dim=args.fourier_dim, **hidden_lists(h))
+    out["dist"], out["args"] = o_dist, oargs
+    out["model"] = VectorFieldNet(out["fourier"], o_dist, oargs.hidden_x, oargs.hidden_t, oargs.hidden_xt, "relu",
+                                  oargs.gradient_clip if dim > 128 else None)
+    return out

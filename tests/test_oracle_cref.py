@@ -5,7 +5,7 @@ attempted-step counts of the adaptive solves equal."""
 import numpy as np
 import pytest
 
-from oracle import cref, flow, fm, mala, ode, prng, targets
+from oracle import cref, flow, fm, loop, mala, metrics, ode, prng, targets
 from tests import gpu_util as gu
 
 
@@ -154,3 +154,250 @@ def test_recorded_step_sequences_and_their_replay_equal_the_numpy_restatement():
     xc, lc = cr.solve(x0, z, +1, 1e-5, 1e-5, 1000, stats=s2, replay=rp)
     assert (s2["n_attempted"] == so["n_attempted"]).all()
     assert np.abs(xc - xo).max() < 1e-11 and np.abs(lc - lo).max() < 1e-10
+
+
+# ---- the mixture and LGCP targets, the exact trace, n_ts = 5 and the metrics' pair sums ----------------------------------------------
+
+def _target_setup(which, B=16, hidden=32, F=16, seed=3):
+    if which == "gmm4":
+        args, dist, k, model, state = gu.gmm4_setup(B=B, hidden=hidden, F=F, seed=seed, hutchs=False)
+    elif which == "gmm16":
+        args, dist, k, model, state = gu.gmm16_setup(B=B, hidden=hidden, F=F, seed=seed, hutchs=False)
+    else:
+        args, dist, k, model, state = gu.lgcp_setup(n=8, B=B, hidden=hidden, F=F, seed=seed)
+    params = gu.rand_params(model, seed=seed, out_scale=0.3)
+    return args, dist, model, params, cref.CRef(model, params)
+
+
+def _points(which, dist, B, seed=0):
+    rng = np.random.default_rng(seed)
+    if which == "lgcp":
+        return dist.mu + rng.standard_normal((B, dist.dim)) @ dist.chol.T
+    return dist.modes[rng.integers(0, len(dist.weights), B)] + 1.5 * rng.standard_normal((B, 2))
+
+
+@pytest.mark.parametrize("which", ["gmm4", "gmm16", "lgcp"])
+def test_mixture_and_lgcp_targets_equal_the_numpy_restatement(which):
+    args, dist, model, params, cr = _target_setup(which)
+    x = _points(which, dist, 24)
+    v = np.random.default_rng(1).standard_normal(x.shape)
+    for temper in (1.0, 0.37):
+        lp, g = targets.Tempered(dist, temper).value_and_grad(x)
+        lpc, gc = cr.value_and_grad(x, temper)
+        assert _rel(lpc, lp) < 1e-12 and _rel(gc, g) < 1e-12, (_rel(lpc, lp), _rel(gc, g))
+    assert _rel(cr.hvp(x, v), dist.hvp_logprob(x, v)) < 1e-12
+
+
+def test_mixture_far_from_every_mode_underflows_as_the_numpy_restatement():
+    """Product of pdfs, then log (distributions.py:59-61): far from every mode the sum underflows to 0 -- log p = -inf, grad = hvp =
+    NaN (0 / 0) -- while nearer points that still underflow PER COMPONENT in one coordinate only keep finite values."""
+    args, dist, model, params, cr = _target_setup("gmm16")
+    x = np.array([[1e3, 1e3], [-60.0, 0.0], [40.0, 3.0], [0.0, 0.0], [25.0, -25.0], [1e8, -1e8]])
+    lp, g = targets.Tempered(dist, 0.5).value_and_grad(x)
+    lpc, gc = cr.value_and_grad(x, 0.5)
+    assert np.isneginf(lp).any() and np.isfinite(lp).any()
+    np.testing.assert_array_equal(np.isneginf(lpc), np.isneginf(lp))
+    np.testing.assert_array_equal(np.isnan(gc), np.isnan(g))
+    f = np.isfinite(lp)
+    assert _rel(lpc[f], lp[f]) < 1e-12 and _rel(gc[f], g[f]) < 1e-12
+    v = np.ones_like(x)
+    h, hc = dist.hvp_logprob(x, v), cr.hvp(x, v)
+    np.testing.assert_array_equal(np.isnan(hc), np.isnan(h))
+    assert _rel(hc[f], h[f]) < 1e-12
+    # the MALA step from a finite state into the underflow region rejects on both sides (NaN delta -> -inf, proposal.py:105)
+    st = mala.MALAState(x[f], lp[f], g[f])
+    noise = np.full((int(f.sum()), 2), 1e3)
+    u = np.full(int(f.sum()), 1e-300)
+    keys = prng.split(prng.PRNGKey(1), int(f.sum()))
+    so, info, _ = mala.kernel(keys, st, targets.Tempered(dist, 0.5).value_and_grad, 0.2, noise=noise)
+    sc, p, acc = cr.mala_step(st, noise, u, 0.2, 0.5)
+    assert not acc.any() and (p == 0).all() and not info.is_accepted.any()
+
+
+@pytest.mark.parametrize("which", ["gmm16", "lgcp"])
+def test_mala_step_on_mixture_and_lgcp_equals_the_numpy_restatement(which):
+    args, dist, model, params, cr = _target_setup(which)
+    x = _points(which, dist, 32)
+    step = 1.5 if which != "lgcp" else 0.01
+    for temper in (1.0, 0.37):
+        vg = targets.Tempered(dist, temper).value_and_grad
+        st0 = mala.init(x, vg)
+        keys = prng.split(prng.PRNGKey(7), 32)
+        a, ia, _ = mala.kernel(keys, st0, vg, step)
+        b, ib = cr.mala_kernel(keys, st0, step, temper)
+        assert (ia.is_accepted == ib.is_accepted).all() and 0 < ia.is_accepted.sum() < 32
+        assert np.abs(ia.acceptance_rate - ib.acceptance_rate).max() < 1e-10
+        assert _rel(b.position, a.position) < 1e-14 and _rel(b.logdensity, a.logdensity) < 1e-12 and _rel(b.logdensity_grad, a.logdensity_grad) < 1e-12
+
+
+@pytest.mark.parametrize("which", ["gmm16", "lgcp"])
+def test_field_jvp_exact_trace_and_loss_on_mixture_and_lgcp_equal_the_numpy_restatement(which):
+    args, dist, model, params, cr = _target_setup(which)
+    rng = np.random.default_rng(2)
+    x, t = _points(which, dist, 16), rng.uniform(0, 1, 16)
+    z = rng.standard_normal(x.shape)
+    v, jv = model.forward(params, x, t, tangent=z)
+    vc, jvc = cr.forward(x, t, tangent=z)
+    assert _rel(vc, v) < 1e-12 and _rel(jvc, jv) < 1e-12
+    if which != "lgcp":
+        assert _rel(cr.jacobian_trace(x, t), model.jacobian_trace(params, x, t)) < 1e-12
+    key = prng.PRNGKey(11)
+    loss, grads = fm.loss_and_grad(model, params, key, x, args.sigma)
+    lc, gc = cr.fm_loss_grad(*fm.cond_flow_batch(key, x, args.sigma))
+    assert abs(lc - loss) < 1e-11 * abs(loss)
+    for a, b in zip(gc, grads):
+        for nm in ("kernel", "bias"):
+            assert np.abs(a[nm].astype(np.float64) - b[nm]).max() <= 2e-7 * max(np.abs(b[nm]).max(), 1e-30), nm
+
+
+@pytest.mark.parametrize("which", ["gmm4", "gmm16"])
+def test_exact_trace_solves_equal_the_numpy_restatement_and_n_ts_keeps_the_step_sequence(which):
+    """The d = 2 configurations' solves (exact trace, exe_flow_matching.py:216-217; 4-mode: n_ts = 5, :347): attempted-step counts equal,
+    the recorded sequences equal, the replay of a float32-rounded sequence equal -- and n_ts = 5 takes exactly the step sequence of n_ts = 2
+    (the attempt counter that restarts per output time bounds only mxstep)."""
+    args, dist, model, params, cr = _target_setup(which, hidden=32, F=16)
+    params = gu.rand_params(model, seed=4, scale=1.0, out_scale=1.0)
+    cr.set_params(params)
+    x0 = _points(which, dist, 12, seed=3)
+    assert args.n_ts == (5 if which == "gmm4" else 2)
+    for sign, f in ((+1, ode.transform_and_logdet), (-1, ode.inverse_and_logdet)):
+        st, sc = {}, {}
+        xo, lo = f(model, params, None, x0, False, args.rtol, args.atol, args.mxstep, n_ts=args.n_ts, stats=st)
+        xc, lc = cr.solve(x0, None, sign, args.rtol, args.atol, args.mxstep, stats=sc, record=400, n_ts=args.n_ts)
+        n = st["n_attempted"]
+        assert n.min() >= 10 and sum(int((~st["acc_seq"][b, :n[b]]).sum()) for b in range(12)) >= 3
+        np.testing.assert_array_equal(sc["n_attempted"], n)
+        assert sc["n_evals_total"] == int((2 + 6 * n).sum())
+        A = st["acc_seq"].shape[1]
+        np.testing.assert_array_equal(sc["acc_seq"][:, :A], st["acc_seq"])
+        # (d + 1 = 3 state components: the error estimate cancels harder than on the wide states above, the controller amplifies the
+        # rounding of the two summation orders: the median step to 1e-9, the worst of several hundred to 3e-4 next to a relu kink)
+        live = st["dt_seq"] > 0
+        rd = np.abs(sc["dt_seq"][:, :A + 1] - st["dt_seq"])[live] / st["dt_seq"][live]
+        assert np.median(rd) < 1e-8 and rd.max() < 1e-3, (np.median(rd), rd.max())
+        np.testing.assert_array_equal(sc["dt_seq"][:, :A + 1] > 0, live)
+        # (measured 1e-8 on gmm4, 7e-7 on gmm16: the relu kinks a solve crosses amplify the rounding difference of the two summation orders)
+        assert np.abs(xc - xo).max() < 1e-5 * max(1.0, np.abs(xo).max()) and np.abs(lc - lo).max() < 1e-5 * max(1.0, np.abs(lo).max())
+        # n_ts: the other number of output times gives the same sequence and the same result, on both sides
+        other = 2 if args.n_ts == 5 else 5
+        st2, sc2 = {}, {}
+        xo2, lo2 = f(model, params, None, x0, False, args.rtol, args.atol, args.mxstep, n_ts=other, stats=st2)
+        xc2, lc2 = cr.solve(x0, None, sign, args.rtol, args.atol, args.mxstep, stats=sc2, record=400, n_ts=other)
+        np.testing.assert_array_equal(st2["acc_seq"], st["acc_seq"]); np.testing.assert_array_equal(st2["dt_seq"], st["dt_seq"])
+        np.testing.assert_array_equal(sc2["acc_seq"], sc["acc_seq"]); np.testing.assert_array_equal(sc2["dt_seq"], sc["dt_seq"])
+        np.testing.assert_array_equal(xc2, xc); np.testing.assert_array_equal(lc2, lc)
+        np.testing.assert_array_equal(xo2, xo); np.testing.assert_array_equal(lo2, lo)
+        # replay
+        rp = dict(dt=st["dt_seq"].astype(np.float32).astype(np.float64), acc=st["acc_seq"])
+        so, s2 = {}, {}
+        xo3, lo3 = f(model, params, None, x0, False, args.rtol, args.atol, args.mxstep, n_ts=args.n_ts, stats=so, replay=rp)
+        xc3, lc3 = cr.solve(x0, None, sign, args.rtol, args.atol, args.mxstep, stats=s2, replay=rp, n_ts=args.n_ts)
+        np.testing.assert_array_equal(s2["n_attempted"], so["n_attempted"])
+        assert np.abs(xc3 - xo3).max() < 1e-11 * max(1.0, np.abs(xo3).max()) and np.abs(lc3 - lo3).max() < 1e-10 * max(1.0, np.abs(lo3).max())
+
+
+def test_mxstep_restarts_per_output_time_as_in_the_numpy_restatement():
+    """The one place n_ts matters: with a tight mxstep the 5-output-time solve gets mxstep attempts per output time."""
+    args, dist, model, params, cr = _target_setup("gmm4", hidden=32, F=16)
+    params = gu.rand_params(model, seed=4, scale=1.0, out_scale=1.0)
+    cr.set_params(params)
+    x0 = _points("gmm4", dist, 8, seed=3)
+    for n_ts in (2, 5):
+        st, sc = {}, {}
+        xo, lo = ode.transform_and_logdet(model, params, None, x0, False, args.rtol, args.atol, 6, n_ts=n_ts, stats=st)
+        xc, lc = cr.solve(x0, None, +1, args.rtol, args.atol, 6, stats=sc, n_ts=n_ts)
+        np.testing.assert_array_equal(sc["n_attempted"], st["n_attempted"])
+        assert np.abs(xc - xo).max() < 1e-9 * max(1.0, np.abs(xo).max())
+        assert st["n_attempted"].max() == (6 if n_ts == 2 else 24) or n_ts == 5 and st["n_attempted"].max() > 6
+
+
+def test_exact_trace_flow_mh_step_on_gmm16_equals_the_numpy_restatement():
+    args, dist, model, params, cr = _target_setup("gmm16", hidden=32, F=16)
+    vg = targets.Tempered(dist, 1.0).value_and_grad
+    st0 = mala.init(_points("gmm16", dist, 12, seed=5), vg)
+    keys = prng.split(prng.PRNGKey(9), 12)
+    so, sc = {}, {}
+    fo, io = flow.rwmh_step(keys, st0, vg, model, params, args, so)
+    fc, ic = cr.rwmh_step(keys, st0, args, stats=sc)
+    np.testing.assert_array_equal(sc["n_att_inv"], so["n_att_inv"]); np.testing.assert_array_equal(sc["n_att_fwd"], so["n_att_fwd"])
+    assert np.abs(sc["log_alpha"] - so["log_alpha"]).max() < 1e-9 * max(1.0, np.abs(so["log_alpha"]).max())
+    assert (ic.is_accepted == io.is_accepted).all() and _rel(fc.position, fo.position) < 1e-10
+
+
+def test_lgcp_hutchinson_solve_equals_the_numpy_restatement():
+    args, dist, model, params, cr = _target_setup("lgcp", hidden=32, F=16)
+    gl = model.zero_layers()[0]                       # unclipped at d = 64: grad log pi is O(10 - 100), the gate scaled down
+    params[gl]["kernel"] *= np.float32(1e-2); params[gl]["bias"] *= np.float32(1e-2)
+    cr.set_params(params)
+    x0 = _points("lgcp", dist, 8, seed=6)
+    z = np.random.default_rng(4).standard_normal(x0.shape)
+    for sign, f in ((+1, ode.transform_and_logdet), (-1, ode.inverse_and_logdet)):
+        st, sc = {}, {}
+        xo, lo = f(model, params, None, x0, True, args.rtol, args.atol, args.mxstep, z=z, stats=st)
+        xc, lc = cr.solve(x0, z, sign, args.rtol, args.atol, args.mxstep, stats=sc)
+        assert st["n_attempted"].min() >= 5
+        np.testing.assert_array_equal(sc["n_attempted"], st["n_attempted"])
+        assert np.abs(xc - xo).max() < 1e-9 * max(1.0, np.abs(xo).max()) and np.abs(lc - lo).max() < 1e-9 * max(1.0, np.abs(lo).max())
+
+
+def test_libmfm_ref_refuses_what_it_does_not_cover():
+    args, dist, model, params, cr = _target_setup("gmm16")
+    x = _points("gmm16", dist, 4)
+    with pytest.raises(AssertionError, match="Hutchinson"):
+        cr.solve(x, np.ones_like(x), +1, 1e-5, 1e-5, 100)
+    a2 = loop.default_args(example="gaussian-mixture", dim=2, num_chain=4, hutchs=False, num_importance_samples=-1)
+    st0 = mala.init(x, targets.Tempered(dist, 1.0).value_and_grad)
+    with pytest.raises(AssertionError, match="IMH"):
+        cr.rwmh_step(prng.split(prng.PRNGKey(1), 4), st0, a2)
+    from oracle.vfield import VectorFieldNet
+    m2 = VectorFieldNet(model.f, dist, model.hidden_x, model.hidden_t, model.hidden_xt, "tanh")
+    with pytest.raises(AssertionError, match="relu"):
+        cref.CRef(m2, params)
+    with pytest.raises(AssertionError, match="targets"):
+        cref.CRef(model, params, target=targets.IndepGaussian(2))
+
+
+@pytest.mark.parametrize("n", [333, 1000])
+def test_stein_and_mmd_pair_sums_equal_the_numpy_restatement(n):
+    args, dist, model, params, cr = _target_setup("gmm16")
+    x, y = _points("gmm16", dist, n, seed=1), _points("gmm16", dist, n, seed=2)
+    g = dist.grad_logprob(x)
+    for beta in (-0.5, -0.3):
+        u, v = cref.stein_disc(x, g, beta)
+        uo, vo = metrics.stein_disc(x, lambda _: g, beta)
+        assert abs(u - uo) < 1e-11 * abs(vo) and abs(v - vo) < 1e-11 * abs(vo)
+    assert abs(cref.max_mean_disc(x, y) - metrics.max_mean_disc(x, y)) < 1e-12
+
+
+# ---- planted errors: each changes the oracle far beyond its agreement with the numpy restatement --------------------------------------
+
+def test_planted_errors_move_the_oracle():
+    """The GPU full-size tests (tests/test_gpu_fullsize_configs.py) require the device to MISS each of these planted oracle errors by 10x
+    its bound; here: each is a real change, orders of magnitude above the C / numpy agreement pinned above."""
+    # one JVP of the exact trace dropped
+    args, dist, model, params, cr = _target_setup("gmm16", hidden=32, F=16)
+    x0 = _points("gmm16", dist, 8, seed=3)
+    _, l_ok = cr.solve(x0, None, +1, args.rtol, args.atol, args.mxstep)
+    _, l_bad = cr.solve(x0, None, +1, args.rtol, args.atol, args.mxstep, drop_jvp=1)
+    assert np.median(np.abs(l_bad - l_ok)) > 1e-4                      # (C vs numpy: 1e-8 above)
+    # one mixture component dropped
+    from oracle.targets import GaussianMixture
+    cut = GaussianMixture(dist.modes[1:], dist.covs[1:], dist.weights[1:])
+    x = _points("gmm16", dist, 64, seed=4)
+    lp, g = cr.value_and_grad(x)
+    lp2, g2 = cref.CRef(model, params, target=cut).value_and_grad(x)
+    assert np.abs(lp2 - lp).max() > 1e-2
+    # the K^-1 term with mu shifted by 1e-3
+    import copy
+    args, dist, model, params, cr = _target_setup("lgcp")
+    sh = copy.copy(dist); sh.mu = dist.mu + 1e-3
+    x = _points("lgcp", dist, 8)
+    lp, g = cr.value_and_grad(x)
+    lp2, g2 = cref.CRef(model, params, target=sh).value_and_grad(x)
+    assert np.abs(g2 - g).max() > 1e-6 * np.abs(g).max()                # (C vs numpy: 1e-12)
+    # the U-statistic without its diagonal removed
+    args, dist, model, params, cr = _target_setup("gmm16")
+    x = _points("gmm16", dist, 500, seed=5)
+    tot, diag = cref.stein_sums(x, dist.grad_logprob(x))
+    u = (tot - diag) / (500 * 499)
+    assert abs(tot / (500 * 499) - u) > 1e-3 * abs(tot / 500 ** 2)
