@@ -107,6 +107,10 @@ int mfm_num_params(const mfm_ctx* ctx);                        /* P_w + P_b */
  * MFM_PHI4: h_params = {a, beta}                                    (PhiFour.__init__, :115-129; Dirichlet 0)
  *           or {a, beta, bc_kind, bc_value}: bc_kind 0 = Dirichlet, both ends held at bc_value (finite);
  *           1 = periodic ring, bc_value ignored.  Any other kind: MFM_EINVAL.
+ *           or {a, beta, bc_kind, bc_value, dim_phys}: dim_phys 1 = the chain (exactly the four-double block), 2 = an L x L
+ *           lattice in row-major order, site (r, c) = element r L + c, cfg.dim = L * L: coefficient a * L, the gradient term over
+ *           the bonds of both axes, each closed by the boundary (periodic: both axes wrap; Dirichlet: a frame held at bc_value).
+ *           dim_phys = 2 with a cfg.dim that is no perfect square, or any other dim_phys: MFM_EINVAL.
  * MFM_GMM : h_params = {n_modes, modes[K*d], stds[K*d], weights[K]} (GaussianMixture, :43-56; stds = sqrt(covs))
  * MFM_LGCP: h_params = {mu, poisson_a, log_norm, counts[d], Kinv[d*d]}  (LogGaussianCoxPines, :233-281) */
 int mfm_set_target(mfm_ctx* ctx, int kind, const double* h_params, size_t n);

@@ -417,9 +417,18 @@ extern "C" int mfm_set_target(mfm_ctx* x, int kind, const double* p, size_t np) 
   memset(&T, 0, sizeof T);
   T.kind = kind; T.dim = d;
   if (kind == MFM_PHI4) {
-    if (np != 2 && np != 4) return fail(MFM_EINVAL, "phi4 target takes {a, beta} or {a, beta, bc_kind, bc_value}");
-    T.coef = (float)(p[0] * d); T.tbeta = (float)p[1];
-    if (np == 4) {      // boundary (distributions.py:130-139): kind 0 = Dirichlet at bc_value, 1 = periodic (bc_value ignored)
+    if (np != 2 && np != 4 && np != 5) return fail(MFM_EINVAL, "phi4 target takes {a, beta}, {a, beta, bc_kind, bc_value} or {a, beta, bc_kind, bc_value, dim_phys}");
+    int side = d;      // the grid side in the coefficient a * side: dim on the chain, L on the L x L lattice (dim_phys = 2, dim = L * L)
+    if (np == 5) {
+      if (p[4] != 1.0 && p[4] != 2.0) return fail(MFM_EINVAL, "phi4 dim_phys must be 1 or 2");
+      if (p[4] == 2.0) {
+        side = (int)std::lround(std::sqrt((double)d));
+        if (side * side != d) return fail(MFM_EINVAL, "phi4 dim_phys = 2 needs a square dim (dim = L * L)");
+        T.lat = side;
+      }
+    }
+    T.coef = (float)(p[0] * side); T.tbeta = (float)p[1];
+    if (np >= 4) {      // boundary (distributions.py:130-139): kind 0 = Dirichlet at bc_value, 1 = periodic (bc_value ignored)
       if (p[2] != 0.0 && p[2] != 1.0) return fail(MFM_EINVAL, "phi4 boundary kind must be 0 (dirichlet) or 1 (periodic)");
       T.bc = p[2] == 1.0 ? MFM_BC_PERIODIC : MFM_BC_DIRICHLET;
       if (T.bc == MFM_BC_DIRICHLET) {

@@ -216,8 +216,9 @@ enum { RM_INIT0 = 0, RM_INIT1 = 1, RM_ATT = 2, RM_DONE = 3 };
 
 // The phi-four boundary of a PHI4_BCRT instance, handed to FTile::eval / eval_c beside the tile (NOT a member: members of the tile
 // change the register allocation of the PHI4_BC0 kernels; an unused argument of an inlined call does not)
-struct Phi4Bc { int bc = MFM_BC_DIRICHLET, d = 0; float bval = 0.f; };
-__device__ __forceinline__ Phi4Bc phi4_bc_of(const NetDev& n) { Phi4Bc p; p.bc = n.T.bc; p.d = n.d; p.bval = n.T.bval; return p; }
+// (lat: the side of a two-dimensional lattice, TargetDev::lat; 0 = the chain)
+struct Phi4Bc { int bc = MFM_BC_DIRICHLET, d = 0; float bval = 0.f; int lat = 0; };
+__device__ __forceinline__ Phi4Bc phi4_bc_of(const NetDev& n) { Phi4Bc p; p.bc = n.T.bc; p.d = n.d; p.bval = n.T.bval; p.lat = n.T.lat; return p; }
 
 template <int D>
 struct FTile {
@@ -518,13 +519,18 @@ struct FTile {
       const float* zr = at(o_xo, S::ZB + i * LDX + 128 * q);
       const float x = xr[0], z = zr[0];
       float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+      float graw, hv;
       if constexpr (BC == PHI4_BCRT) {
         const int col = 16 * wave + c + 128 * q;
-        phi4_nb(pb.bc, pb.bval, xr, col, pb.d, xl, xp);
-        phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, zl, zp);
+        float xu, zu;
+        const float cf = phi4_nbs(pb.bc, pb.bval, xr, col, pb.d, pb.lat, xl, xp, xu);
+        phi4_nbs<true>(pb.bc, pb.bval, zr, col, pb.d, pb.lat, zl, zp, zu);
+        graw = -tbeta * (coef * (cf * x - xl - xp - xu) - x * (1.f - x * x) * icoef);
+        hv = -tbeta * (coef * (cf * z - zl - zp - zu) - (1.f - 3.f * x * x) * z * icoef);
+      } else {
+        graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+        hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
       }
-      const float graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
-      const float hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
       gc[q][i] = clip > 0.f ? fminf(fmaxf(graw, -clip), clip) : graw;
       hz[q][i] = (!(clip > 0.f) || fabsf(graw) <= clip) ? hv : 0.f;
       zz[q][i] = z;
@@ -555,8 +561,11 @@ struct FTile {
         const int w0 = W(S::W2, wave, D / 16), wnx = W(S::W3, wave, 8);
         const float ntb = -tbeta;
         typedef float f32x2 __attribute__((ext_vector_type(2)));
-        f32x2 ox[2][6];                           // [buffer][x, x-, x+, z, z-, z+] of the pair's two elements
-        auto tt_fetch = [&](int p, f32x2 (&o)[6]) {
+        constexpr int NO = BC == PHI4_BCRT ? 8 : 6;      // (PHI4_BCRT: + the up + down sums of x and z, 0 on the chain)
+        f32x2 ox[2][NO];                          // [buffer][x, x-, x+, z, z-, z+] of the pair's two elements
+        [[maybe_unused]] float cf = 2.f;          // centre weight of the Laplacian (PHI4_BCRT: 4 on the lattice)
+        if constexpr (BC == PHI4_BCRT) cf = phi4_2d(pb.lat) ? 4.f : 2.f;
+        auto tt_fetch = [&](int p, f32x2 (&o)[NO]) {
           const int q = p >> 1, i0 = 2 * (p & 1);
 #pragma unroll
           for (int e = 0; e < 2; ++e) {
@@ -565,9 +574,9 @@ struct FTile {
             o[0][e] = xr[0]; o[1][e] = xr[-1]; o[2][e] = xr[1]; o[3][e] = zr[0]; o[4][e] = zr[-1]; o[5][e] = zr[1];
             if constexpr (BC == PHI4_BCRT) {
               const int col = 16 * wave + c + 128 * q;
-              float l, r;
-              phi4_nb(pb.bc, pb.bval, xr, col, pb.d, l, r); o[1][e] = l; o[2][e] = r;
-              phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, l, r); o[4][e] = l; o[5][e] = r;
+              float l, r, ud;
+              phi4_nbs(pb.bc, pb.bval, xr, col, pb.d, pb.lat, l, r, ud); o[1][e] = l; o[2][e] = r; o[6][e] = ud;
+              phi4_nbs<true>(pb.bc, pb.bval, zr, col, pb.d, pb.lat, l, r, ud); o[4][e] = l; o[5][e] = r; o[7][e] = ud;
             }
           }
         };
@@ -576,10 +585,15 @@ struct FTile {
         // instructions, took as long inside the job as the packed 110 had taken in front of it)
         f32x2 lx, lz, ax, bz, gr, hv;
         const f32x2 two = {2.f, 2.f}, one = {1.f, 1.f}, three = {3.f, 3.f}, ic2 = {icoef, icoef}, co2 = {coef, coef}, nt2 = {ntb, ntb};
-        auto piece = [&](int p, int k, const f32x2 (&o)[6]) {
+        auto piece = [&](int p, int k, const f32x2 (&o)[NO]) {
           const int q = p >> 1, i0 = 2 * (p & 1);
           const f32x2 x = o[0], z = o[3];
-          if (k == 0) { lx = __builtin_elementwise_fma(x, two, -o[1]) - o[2]; lz = __builtin_elementwise_fma(z, two, -o[4]) - o[5]; }
+          if constexpr (BC == PHI4_BCRT) {
+            const f32x2 cf2 = {cf, cf};
+            if (k == 0) { lx = __builtin_elementwise_fma(x, cf2, -o[1]) - o[2] - o[6]; lz = __builtin_elementwise_fma(z, cf2, -o[4]) - o[5] - o[7]; }
+          } else {
+            if (k == 0) { lx = __builtin_elementwise_fma(x, two, -o[1]) - o[2]; lz = __builtin_elementwise_fma(z, two, -o[4]) - o[5]; }
+          }
           if (k == 1) ax = ic2 * (x * __builtin_elementwise_fma(-x, x, one));
           if (k == 2) { gr = __builtin_elementwise_fma(co2, lx, -ax) * nt2; bz = ic2 * (z * __builtin_elementwise_fma(-x, x * three, one)); }
           if (k == 3) hv = __builtin_elementwise_fma(co2, lz, -bz) * nt2;
@@ -762,13 +776,18 @@ struct FTile {
           const float* zr = xr + 8 * LDX;
           const float x = xr[0], z = zr[0];
           float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+          float graw, hv;
           if constexpr (BC == PHI4_BCRT) {
             const int col = 16 * wave + c + 128 * q;
-            phi4_nb(pb.bc, pb.bval, xr, col, pb.d, xl, xp);
-            phi4_nb<true>(pb.bc, pb.bval, zr, col, pb.d, zl, zp);
+            float xu, zu;
+            const float cf = phi4_nbs(pb.bc, pb.bval, xr, col, pb.d, pb.lat, xl, xp, xu);
+            phi4_nbs<true>(pb.bc, pb.bval, zr, col, pb.d, pb.lat, zl, zp, zu);
+            graw = -tbeta * (coef * (cf * x - xl - xp - xu) - x * (1.f - x * x) * icoef);
+            hv = -tbeta * (coef * (cf * z - zl - zp - zu) - (1.f - 3.f * x * x) * z * icoef);
+          } else {
+            graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+            hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
           }
-          const float graw = -tbeta * (coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
-          const float hv = -tbeta * (coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
           gc[q][i] = clip > 0.f ? fminf(fmaxf(graw, -clip), clip) : graw;
           hz[q][i] = (!(clip > 0.f) || fabsf(graw) <= clip) ? hv : 0.f;
           zz[q][i] = z;
@@ -1308,7 +1327,7 @@ struct TailArgs {
 __device__ __forceinline__ int true_dim(const TailArgs& a) { return a.d_true; }
 // with the phi-four boundary of a PHI4_BCRT instance; the PHI4_BC0 instances take TailArgs itself (a derived type, even an empty one,
 // is passed differently to the non-inlined tail and changed the main loop's allocation)
-struct TailArgsBC : TailArgs { int bc; float bval; };
+struct TailArgsBC : TailArgs { int bc; float bval; int lat; };
 template <int BC> using TailArgsT = typename std::conditional<BC == PHI4_BC0, TailArgs, TailArgsBC>::type;
 // NOT inlined: inlined into solve2, the three loops changed the register allocation of the MAIN loop (its Runge-Kutta stages went
 // to scratch: 50 -> 63 ms).  As functions they get an allocation of their own and the main loop keeps the one it had.
@@ -1561,13 +1580,18 @@ __device__ __noinline__ void solve2_tail(TailArgsT<BC> a, int b0) {
               const float* zr = xr + 2 * LDX;
               const float x = xr[0], z = zr[0];
               float xl = xr[-1], xp = xr[1], zl = zr[-1], zp = zr[1];
+              float graw, hv;
               if constexpr (BC == PHI4_BCRT) {
                 const int col = colw + 128 * q;
-                phi4_nb(a.bc, a.bval, xr, col, a.d_true, xl, xp);
-                phi4_nb<true>(a.bc, a.bval, zr, col, a.d_true, zl, zp);
+                float xu, zu;
+                const float cf = phi4_nbs(a.bc, a.bval, xr, col, a.d_true, a.lat, xl, xp, xu);
+                phi4_nbs<true>(a.bc, a.bval, zr, col, a.d_true, a.lat, zl, zp, zu);
+                graw = -t_beta * (t_coef * (cf * x - xl - xp - xu) - x * (1.f - x * x) * icoef);
+                hv = -t_beta * (t_coef * (cf * z - zl - zp - zu) - (1.f - 3.f * x * x) * z * icoef);
+              } else {
+                graw = -t_beta * (t_coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
+                hv = -t_beta * (t_coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
               }
-              const float graw = -t_beta * (t_coef * (2.f * x - xl - xp) - x * (1.f - x * x) * icoef);
-              const float hv = -t_beta * (t_coef * (2.f * z - zl - zp) - (1.f - 3.f * x * x) * z * icoef);
               gc[p][q] = t_clip > 0.f ? fminf(fmaxf(graw, -t_clip), t_clip) : graw;
               hz[p][q] = (!(t_clip > 0.f) || fabsf(graw) <= t_clip) ? hv : 0.f;
               zz[p][q] = z;
@@ -2068,7 +2092,7 @@ __device__ __forceinline__ void solve2(FTile<D>& T, const OdeArgs& a, const Flow
       const unsigned long long tl0_ = __builtin_amdgcn_s_memtime();
 #endif
       TailArgsT<BC> ta;
-      if constexpr (BC == PHI4_BCRT) { ta.bc = a.net.T.bc; ta.bval = a.net.T.bval; }
+      if constexpr (BC == PHI4_BCRT) { ta.bc = a.net.T.bc; ta.bval = a.net.T.bval; ta.lat = a.net.T.lat; }
       ta.rtol = a.rtol; ta.atol = a.atol; ta.max_attempts = a.max_attempts; ta.d_true = a.net.d;
       ta.coef = a.net.T.coef; ta.tbeta = a.net.T.tbeta; ta.clip = a.net.grad_clip; ta.fourier = a.net.fourier; ta.Wp = a.net.Wp;
       ta.zgen = a.zgen; ta.z2 = a.z2; ta.mode = fmode; ta.ref_std = f.ref_std; ta.rp = a.rp;

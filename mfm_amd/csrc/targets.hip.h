@@ -10,6 +10,8 @@
 // tangent row's ends see 0 (Dirichlet, any b) or its other end (periodic).  The pads are never read there, so
 // they stay zero whatever the boundary, rows of different kinds may share them, and the zero state columns
 // d .. D-1 of a narrower lattice on a wider tile are never taken for a neighbour.
+// The two-dimensional lattice (TargetDev::lat = L, d = L * L, site (r, c) = element r L + c) is served by the same by-index forms:
+// four neighbours, each axis with the boundary above (phi4_nb4; phi4_nbs picks the chain or the lattice at run time).
 #pragma once
 #include "common.hip.h"
 
@@ -41,8 +43,14 @@ struct TargetDev {
   // phi4 boundary (distributions.py:130-139): MFM_BC_DIRICHLET with both ends held at bval, or MFM_BC_PERIODIC (bval unused)
   int bc;
   float bval;
+  // phi4 lattice: side L of an L x L field in row-major order (dim_phys = 2, dim = L * L, coef = a * L); 0: the 1-D chain.
+  // (fills the struct's tail padding: no kernel argument moves)
+  int lat;
 };
-__host__ __device__ __forceinline__ bool phi4_default_bc(const TargetDev& T) { return T.bc == MFM_BC_DIRICHLET && T.bval == 0.f; }
+static_assert(sizeof(TargetDev) == 104, "TargetDev::lat sits in the tail padding: the kernel argument layouts are those without it");
+__host__ __device__ __forceinline__ bool phi4_2d(int lat) { return lat > 0; }
+// Dirichlet 0 on the 1-D chain: the only context the zero pads (the PHI4_BC0 instances) serve
+__host__ __device__ __forceinline__ bool phi4_default_bc(const TargetDev& T) { return T.bc == MFM_BC_DIRICHLET && T.bval == 0.f && !phi4_2d(T.lat); }
 
 // ---- PhiFour --------------------------------------------------------------------------------------
 // loglik terms of element j (to be summed over j): -beta (coef/2 (x_{j+1}-x_j)^2 [+ left edge] + (1-x^2)^2/(4 coef))
@@ -79,13 +87,60 @@ __device__ __forceinline__ void phi4_nb(int bc, float bval, const float* p, int 
   l = j > 0 ? p[-1] : (per ? p[d - 1] : e);
   r = j + 1 < d ? p[1] : (per ? p[1 - d] : e);
 }
+// The L x L lattice: left / right along the row of the lattice, up / down one row of it (j -+ L), each axis closed by the same
+// boundary.  Every read stays inside elements 0 .. d-1 of the row; an element beyond d (tile padding) reads nothing.
+template <bool PROBE = false>
+__device__ __forceinline__ void phi4_nb4(int bc, float bval, const float* p, int j, int d, int L, float& l, float& r, float& u, float& dn) {
+  const bool per = bc == MFM_BC_PERIODIC;
+  const float e = PROBE ? 0.f : bval;
+  l = r = u = dn = 0.f;
+  if (j < d) {
+    const int c = (int)((unsigned)j % (unsigned)L);
+    l = c > 0 ? p[-1] : (per ? p[L - 1] : e);
+    r = c + 1 < L ? p[1] : (per ? p[1 - L] : e);
+    u = j >= L ? p[-L] : (per ? p[d - L] : e);
+    dn = j + L < d ? p[L] : (per ? p[L - d] : e);
+  }
+}
+// Chain or lattice at run time (lat: TargetDev::lat): returns the centre weight cf (2 or 4) of the Laplacian cf x - l - r - ud,
+// ud = up + down (0.f on the chain, where the form rounds exactly as 2 x - l - r)
+template <bool PROBE = false>
+__device__ __forceinline__ float phi4_nbs(int bc, float bval, const float* p, int j, int d, int lat, float& l, float& r, float& ud) {
+  if (phi4_2d(lat)) {
+    float u, dn;
+    phi4_nb4<PROBE>(bc, bval, p, j, d, lat, l, r, u, dn);
+    ud = u + dn;
+    return 4.f;
+  }
+  phi4_nb<PROBE>(bc, bval, p, j, d, l, r);
+  ud = 0.f;
+  return 2.f;
+}
 __device__ __forceinline__ float phi4_grad_bc(const TargetDev& T, const float* xs, int j, int d) {
-  float x = xs[j], l, r;
-  phi4_nb(T.bc, T.bval, xs + j, j, d, l, r);
-  float lap = 2.f * x - l - r;
+  float x = xs[j], l, r, ud;
+  const float cf = phi4_nbs(T.bc, T.bval, xs + j, j, d, T.lat, l, r, ud);
+  float lap = cf * x - l - r - ud;
   return -T.tbeta * __builtin_fmaf(T.coef, lap, -(x * __builtin_fmaf(-x, x, 1.f) / T.coef));
 }
+// lattice: the right and the down bond of every site, plus the left / top frame bond of column 0 / row 0 under Dirichlet
+// (periodic: 2 d bonds, Dirichlet: 2 L (L + 1))
+__device__ __forceinline__ double phi4_term_2d(const TargetDev& T, const float* xs, int j, int d) {
+  const int L = T.lat;
+  double x = xs[j];
+  float l, r, up, dn;
+  phi4_nb4(T.bc, T.bval, xs + j, j, d, L, l, r, up, dn);
+  double dr = (double)r - x, dd = (double)dn - x;
+  double u = __builtin_fma(dd, dd, dr * dr);
+  if (T.bc != MFM_BC_PERIODIC) {
+    const double xb = x - (double)T.bval;
+    if ((unsigned)j % (unsigned)L == 0) u = __builtin_fma(xb, xb, u);
+    if (j < L) u = __builtin_fma(xb, xb, u);
+  }
+  double q = __builtin_fma(-x, x, 1.0);
+  return -(double)T.tbeta * __builtin_fma(0.5 * (double)T.coef, u, q * q / (4.0 * (double)T.coef));
+}
 __device__ __forceinline__ double phi4_term_bc(const TargetDev& T, const float* xs, int j, int d) {
+  if (phi4_2d(T.lat)) return phi4_term_2d(T, xs, j, d);
   // bond (j, j+1) with x_d from the boundary; the left bond (x_0 - b)^2 for j == 0 under Dirichlet only (periodic: d bonds)
   double x = xs[j];
   float l, r;
@@ -97,9 +152,9 @@ __device__ __forceinline__ double phi4_term_bc(const TargetDev& T, const float* 
   return -(double)T.tbeta * __builtin_fma(0.5 * (double)T.coef, u, q * q / (4.0 * (double)T.coef));
 }
 __device__ __forceinline__ float phi4_hvp_bc(const TargetDev& T, const float* xs, const float* vs, int j, int d) {
-  float x = xs[j], v = vs[j], l, r;
-  phi4_nb<true>(T.bc, T.bval, vs + j, j, d, l, r);
-  float lap = 2.f * v - l - r;
+  float x = xs[j], v = vs[j], l, r, ud;
+  const float cf = phi4_nbs<true>(T.bc, T.bval, vs + j, j, d, T.lat, l, r, ud);
+  float lap = cf * v - l - r - ud;
   return -T.tbeta * (T.coef * lap - (1.f - 3.f * x * x) * v / T.coef);
 }
 

@@ -619,14 +619,15 @@ __global__ __launch_bounds__(256) void target_kernel(TgtArgs a) {
       float graw, hraw = 0.f;
       if (a.T.kind == MFM_TARGET_PHI4) {
         float xl = col > 0 ? a.X[idx - 1] : 0.f, xr = col + 1 < a.d ? a.X[idx + 1] : 0.f;
-        if constexpr (BCRT) phi4_nb(a.T.bc, a.T.bval, a.X + idx, col, a.d, xl, xr);      // (by index: Dirichlet b or periodic)
-        graw = -a.T.tbeta * (a.T.coef * (2.f * x - xl - xr) - x * (1.f - x * x) / a.T.coef);
-        if (a.diag) hraw = -a.T.tbeta * (a.T.coef * 2.f - (1.f - 3.f * x * x) / a.T.coef);
+        float cf = 2.f, xu = 0.f;      // (BCRT: centre weight 4 and the up + down sum on the two-dimensional lattice)
+        if constexpr (BCRT) cf = phi4_nbs(a.T.bc, a.T.bval, a.X + idx, col, a.d, a.T.lat, xl, xr, xu);      // (by index: Dirichlet b or periodic)
+        graw = -a.T.tbeta * (a.T.coef * (cf * x - xl - xr - xu) - x * (1.f - x * x) / a.T.coef);
+        if (a.diag) hraw = -a.T.tbeta * (a.T.coef * cf - (1.f - 3.f * x * x) / a.T.coef);
         else if (a.Z) {
           const float v = a.Z[zi];
-          float vl = col > 0 ? a.Z[zi - 1] : 0.f, vr = col + 1 < a.d ? a.Z[zi + 1] : 0.f;
-          if constexpr (BCRT) phi4_nb<true>(a.T.bc, a.T.bval, a.Z + zi, col, a.d, vl, vr);
-          hraw = -a.T.tbeta * (a.T.coef * (2.f * v - vl - vr) - (1.f - 3.f * x * x) * v / a.T.coef);
+          float vl = col > 0 ? a.Z[zi - 1] : 0.f, vr = col + 1 < a.d ? a.Z[zi + 1] : 0.f, vu = 0.f;
+          if constexpr (BCRT) phi4_nbs<true>(a.T.bc, a.T.bval, a.Z + zi, col, a.d, a.T.lat, vl, vr, vu);
+          hraw = -a.T.tbeta * (a.T.coef * (cf * v - vl - vr - vu) - (1.f - 3.f * x * x) * v / a.T.coef);
         }
       } else {
         const float ex = a.T.poisson_a * expf(x);
@@ -1068,6 +1069,7 @@ __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
   if (a.T.kind == MFM_TARGET_PHI4) {
     double part = 0.0;
     for (int col = lane; col < a.d; col += 64) {
+      if constexpr (BCRT) if (phi4_2d(a.T.lat)) { part += phi4_term_2d(a.T, y, col, a.d); continue; }
       const double x = y[col];
       double xr = col + 1 < a.d ? (double)y[col + 1] : 0.0;
       if constexpr (BCRT) if (col + 1 >= a.d) xr = a.T.bc == MFM_BC_PERIODIC ? (double)y[0] : (double)a.T.bval;
@@ -1111,8 +1113,9 @@ __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
       float gv;
       if (a.T.kind == MFM_TARGET_PHI4) {
         float xl = col > 0 ? y[col - 1] : 0.f, xr = col + 1 < a.d ? y[col + 1] : 0.f;
-        if constexpr (BCRT) phi4_nb(a.T.bc, a.T.bval, y + col, col, a.d, xl, xr);
-        gv = (float)a.beta * (-a.T.tbeta * (a.T.coef * (2.f * xv - xl - xr) - xv * (1.f - xv * xv) / a.T.coef));
+        float cf = 2.f, xu = 0.f;
+        if constexpr (BCRT) cf = phi4_nbs(a.T.bc, a.T.bval, y + col, col, a.d, a.T.lat, xl, xr, xu);
+        gv = (float)a.beta * (-a.T.tbeta * (a.T.coef * (cf * xv - xl - xr - xu) - xv * (1.f - xv * xv) / a.T.coef));
       } else if (a.T.kind == MFM_TARGET_GMM) {
         gv = 0.f;
 #pragma unroll

@@ -11,6 +11,7 @@ target descriptor + temperature.  Anything else a user-written closure might com
 Called on a CUDA tensor ``[B, d]`` the methods evaluate on the device through the engine the distribution is
 attached to.
 """
+import math
 import os
 
 import numpy as np
@@ -107,12 +108,20 @@ class Distribution:
 
 class PhiFour(Distribution):
     """``distributions.py:114-165``: ``bc=('dirichlet', b)`` holds both ends at b (d + 1 bonds), ``bc=('pbc', .)`` closes the
-    lattice into a ring (d bonds; the value is ignored).  The ``tilt`` branch is dead in the reference and is not built."""
+    lattice into a ring (d bonds; the value is ignored).  The ``tilt`` branch is dead in the reference and is not built.
+
+    ``dim_phys=2`` (a build-side definition, after ``PhiFourBase``'s ``dim_phys == 2`` branch): the row is an L x L field in
+    row-major order, ``dim = L * L``, the coefficient is ``a * L``, the gradient term sums the bonds of both axes -- ``pbc`` wraps
+    both (2 L^2 bonds), ``dirichlet b`` surrounds the lattice by a frame held at b (2 L (L + 1) bonds)."""
 
     kind = "phi4"
     BC_KINDS = {"dirichlet": 0, "pbc": 1}
 
-    def __init__(self, dim, a=0.1, beta=20.0, bc=("dirichlet", 0), tilt=None):
+    def __init__(self, dim, a=0.1, beta=20.0, bc=("dirichlet", 0), tilt=None, dim_phys=1):
+        if dim_phys not in (1, 2):
+            raise ValueError(f"PhiFour dim_phys must be 1 or 2, got {dim_phys!r}")
+        if dim_phys == 2 and math.isqrt(int(dim)) ** 2 != int(dim):
+            raise ValueError(f"PhiFour dim_phys = 2 needs a square dim (dim = L * L), got {dim}")
         if tilt is not None:
             raise NotImplementedError("the tilted PhiFour is not built (its branch reads an undefined attribute in the reference)")
         name, value = bc[0], bc[1]
@@ -124,12 +133,17 @@ class PhiFour(Distribution):
                 raise ValueError(f"the Dirichlet boundary value must be finite, got {value}")
         self.dim, self.a, self.beta = int(dim), a, beta
         self.bc = (name, value)
+        self.dim_phys = int(dim_phys)
+        self.dim_grid = math.isqrt(self.dim) if self.dim_phys == 2 else self.dim      # the side in the coefficient a * dim_grid
         self.log_Z, self.n_plots, self.can_sample = 0.0, 0, False
 
     def target_block(self):
         """``[a, beta]`` for Dirichlet 0 (the block every context had before boundaries existed); otherwise
-        ``[a, beta, kind, b]`` with kind 0 = Dirichlet at b, 1 = periodic (b = 0, unused)."""
+        ``[a, beta, kind, b]`` with kind 0 = Dirichlet at b, 1 = periodic (b = 0, unused); ``dim_phys = 2`` appends it:
+        ``[a, beta, kind, b, 2]``."""
         name, value = self.bc
+        if self.dim_phys == 2:
+            return 0, [self.a, self.beta, float(self.BC_KINDS[name]), float(value) if name == "dirichlet" else 0.0, 2.0]
         if name == "dirichlet" and value == 0:
             return 0, [self.a, self.beta]
         return 0, [self.a, self.beta, float(self.BC_KINDS[name]), float(value) if name == "dirichlet" else 0.0]

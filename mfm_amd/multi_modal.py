@@ -43,7 +43,8 @@ def main(args):
         args.lim, args.num_chain, args.eval_iter, args.step_size = [-1.6, 1.6], 1024, 1, 0.0001
         if args.force_dim:
             args.dim = args.force_dim
-        dist = PhiFour(args.dim, bc=(getattr(args, 'phi4_bc', 'dirichlet'), getattr(args, 'phi4_bc_value', 0.0)))
+        dist = PhiFour(args.dim, bc=(getattr(args, 'phi4_bc', 'dirichlet'), getattr(args, 'phi4_bc_value', 0.0)),
+                       dim_phys=getattr(args, 'phi4_dim_phys', 1))      # (a non-square dim with --phi4_dim_phys 2: ValueError)
         dist.sample_model = None
     elif args.example == "4-mode":                                                      # :65-85
         print("Setting up 4-mode Gaussian mixture density...")
@@ -159,6 +160,9 @@ def build_parser():
     # --phi4_bc_value, or a periodic ring (--phi4_bc pbc; the value is ignored)
     parser.add_argument('--phi4_bc', type=str, default='dirichlet', choices=['dirichlet', 'pbc'])
     parser.add_argument('--phi4_bc_value', type=float, default=0.0)
+    # the phi-four field's physical dimension: 1 = the chain of the reference's main script, 2 = an L x L lattice in row-major order
+    # (dim = L * L must be a perfect square; coefficient a * L, the boundary on both axes)
+    parser.add_argument('--phi4_dim_phys', type=int, default=1, choices=[1, 2])
     return parser
 
 

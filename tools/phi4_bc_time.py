@@ -1,16 +1,17 @@
 """Cost of the phi-four boundary on the headline shape: d = 256, 4096 chains, widths 128, --hutch (the shape-specialised solver and
 the static training kernel), with the same network, chains and keys for Dirichlet 0 (the default PHI4_BC0 kernels), Dirichlet 1
-and periodic (the PHI4_BCRT instances, targets.hip.h).  Per boundary:
+and periodic (the PHI4_BCRT instances, targets.hip.h), and for the 16 x 16 lattice (dim_phys = 2: the same PHI4_BCRT instances with
+four neighbours by index) under periodic and Dirichlet-0 boundaries.  Per row:
 
   flow step, adaptive Dopri5   (RWMH, two solves per chain; attempted steps per chain printed beside the time)
   flow step, fixed RK4 x 16    (the like-for-like comparison: every boundary does the same number of evaluations)
   training iteration           (mfm_train_iter: the fused MALA step + flow-matching loss / gradient + AdamW)
 
-The three boundaries' contexts exist side by side: each gets `--warmup` untimed calls, then `--reps` rounds time every boundary once,
+The rows' contexts exist side by side: each gets `--warmup` untimed calls, then `--reps` rounds time every boundary once,
 in rotating order, with HIP events around the call on the default stream after a synchronisation.  The median and the min..max spread
 are printed; the raw times go to `--out`.  (The flow step is timed with its chain reset and mala_init, whose own median is subtracted.)
 
-    python tools/phi4_bc_time.py [--reps 15] [--warmup 5] [--out profiles/r07_phi4_bc_time.json]
+    python tools/phi4_bc_time.py [--reps 15] [--warmup 5] [--out profiles/r08_phi4_2d_time.json]
 """
 import argparse
 import json
@@ -20,7 +21,8 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
-BCS = [("dirichlet-0", None), ("dirichlet-1", [0.0, 1.0]), ("periodic", [1.0, 0.0])]
+BCS = [("dirichlet-0", None), ("dirichlet-1", [0.0, 1.0]), ("periodic", [1.0, 0.0]),
+       ("2d-periodic", [1.0, 0.0, 2.0]), ("2d-dirichlet-0", [0.0, 0.0, 2.0])]
 
 
 def _ctx(bc_tail, **kw):
@@ -138,6 +140,9 @@ def main():
         ratio = float(np.median(np.array(r["rk4x16_ms"]) / np.array(d0["rk4x16_ms"])))      # per round (paired: same round, adjacent calls)
         tr = fmt(r["train_iter_ms"])
         print(f"{name:12s} {fmt(r['dopri5_ms']):>28s} {r['dopri5_attempts_per_chain']:9.1f} {fmt(r['rk4x16_ms']):>28s} {ratio:6.3f} {tr:>26s}")
+    # the like-for-like cost of the lattice: 2-D periodic against 1-D periodic, RK4 x 16, per round
+    r2 = np.array(res["2d-periodic"]["rk4x16_ms"]) / np.array(res["periodic"]["rk4x16_ms"])
+    print(f"rk4x16 flow step, 2d-periodic / periodic: median {np.median(r2):.3f} [{r2.min():.3f}..{r2.max():.3f}]")
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
