@@ -8,8 +8,10 @@
 // a categorical draw over [w_0, w_1 .. w_n] (:290-292; jax.random.choice = inverse CDF at cumsum[-1] (1 - U)) and the
 // state update (:293-295; the gradient of the previous state is kept as is, a quirk of the reference).
 // One wavefront per chain, float64 weights (they span hundreds of orders of magnitude before normalisation), weights
-// are normalised by their sum exactly as the reference does (no max subtraction: overflow -> NaN -> the reference's
-// behaviour is reproduced, index 0 is chosen by searchsorted on an all-NaN table).
+// are normalised by their sum exactly as the reference does (no max subtraction), so a table may vanish, overflow or hold NaN.
+// The search then follows searchsorted's order, NaN last and equal to itself (search_lt, common.hip.h): every weight vanishing
+// (0 / 0) or a NaN weight gives an all-NaN table and index 0, the current state is kept; an overflowing weight gives
+// [0 .. 0, NaN, NaN ..] with a NaN query, and the FIRST overflowing entry is selected.
 #include "prng.hip.h"
 
 struct CisArgs {
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void cis_select_kernel(CisArgs a) {
   }
   const Key2 kb = split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b);                            // :303
   const double u = uniform01(split_at(kb, 4, 3), 0, 1);                                                 // key_choice (:281, :292)
-  // p = w / tot; p_cuml = cumsum(p); r = p_cuml[-1] (1 - u); first index with p_cuml[idx] >= r
+  // p = w / tot; p_cuml = cumsum(p); r = p_cuml[-1] (1 - u); first index with not p_cuml[idx] < r in searchsorted's order
   double cum = w0 / tot, cum_last = 0.0;
   {
     double c = w0 / tot;
@@ -51,13 +53,13 @@ __global__ __launch_bounds__(256) void cis_select_kernel(CisArgs a) {
   }
   const double rr = cum_last * (1.0 - u);
   int choice = 0; double wsel = w0 / tot;
-  if (!(cum >= rr)) {
+  if (search_lt(cum, rr)) {
     choice = n;                                         // searchsorted returns len(p) when nothing qualifies -> clamp (gather clamps)
     for (int j = 0; j < n; ++j) {
       const size_t r = (size_t)b * n + j;
       const double pj = exp(a.lps[r] - refl(a.refs + r * d) - (double)a.vols[r]) / tot;
       cum += pj;
-      if (cum >= rr) { choice = j + 1; wsel = pj; break; }
+      if (!search_lt(cum, rr)) { choice = j + 1; wsel = pj; break; }
       if (j == n - 1) wsel = pj;
     }
   }

@@ -74,6 +74,9 @@ __device__ __forceinline__ double wave_max(double v) {
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
   return v;
 }
+// The order of numpy / jax searchsorted: NaN sorts LAST and equal to itself.  An inverse-CDF search is "first i with not
+// search_lt(cum_i, r)": a NaN query stops at the table's first NaN (0 on an all-NaN table), a finite one at the first NaN at the latest.
+__device__ __forceinline__ bool search_lt(double a, double b) { return a < b || (isnan(b) && !isnan(a)); }
 // sum over the 16 lanes that share (lane >> 4)
 __device__ __forceinline__ float group16_sum(float v) {
 #pragma unroll

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(SMC_THREADS) void smc_delta_kernel(const double* ll
     }
     res = a;
   } else res = NAN;
-  if (threadIdx.x == 0) out[0] = fmin(fmax(res, 0.0), max_delta);      // adaptive_tempered.py:70 (clip; NaN propagates)
+  if (threadIdx.x == 0) out[0] = isnan(res) ? res : fmin(fmax(res, 0.0), max_delta);      // adaptive_tempered.py:70 (clip; NaN propagates there, fmax / fmin would drop it)
 }
 
 __global__ __launch_bounds__(SMC_THREADS) void smc_weights_kernel(const double* ll, int n, double delta, double* weights, double* lognorm) {
@@ -119,9 +119,10 @@ __global__ __launch_bounds__(SMC_THREADS) void smc_resample2_kernel(int scheme, 
 // searchsorted(p_cuml, r) (side = 'left').  Sequential cumulative sum for the same reason as above.
 __global__ __launch_bounds__(SMC_THREADS) void choice_logw_kernel(Key2 key, const double* logw, int n, int m, double* cum, int* idx) {
   __shared__ double sm[SMC_THREADS / 64];
-  double mx = -INFINITY;
-  for (int i = threadIdx.x; i < n; i += SMC_THREADS) mx = fmax(mx, logw[i]);          // jnp.max: a NaN weight poisons the draw there too
+  double mx = -INFINITY, n_nan = 0.0;
+  for (int i = threadIdx.x; i < n; i += SMC_THREADS) { mx = fmax(mx, logw[i]); n_nan += isnan(logw[i]) ? 1.0 : 0.0; }
   mx = smc_block_reduce(mx, sm, true);
+  if (smc_block_reduce(n_nan, sm, false) > 0.0) mx = NAN;                             // jnp.max propagates a NaN (fmax drops it): the whole table is poisoned, as there
   for (int i = threadIdx.x; i < n; i += SMC_THREADS) cum[i] = exp(logw[i] - mx);      // :458
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(SMC_THREADS) void choice_logw_kernel(Key2 key, cons
     int lo = 0, hi = n;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (cum[mid] < r) lo = mid + 1; else hi = mid;
+      if (search_lt(cum[mid], r)) lo = mid + 1; else hi = mid;   // NaN last: a +inf log-weight leaves [0 .. 0, NaN ..] and r = NaN -> that entry
     }
     idx[j] = lo < n - 1 ? lo : n - 1;
   }

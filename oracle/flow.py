@@ -80,22 +80,17 @@ def imh_step(keys, prev, value_and_grad, model, params, args, stats=None, replay
     return _accept(kk[:, 1], a, prev, (xp, lpn, gn))
 
 
-def cis_step(keys, prev, value_and_grad, model, params, args, stats=None):
-    """``exe_flow_matching.py:280-296``: conditional importance sampling with ``args.num_importance_samples`` fresh
-    flow samples per chain.  Quirk kept: an accepted state carries the STALE ``prev_state.logdensity_grad`` (``:295``)."""
-    B, d = prev.position.shape
-    n_is = int(args.num_importance_samples)
-    ref = IndepGaussian(d, var=REF_VARS[getattr(args, "ref_dist", "stdgauss")])
+def cis_select(keys, prev, u0, vol0, refs, xs, vols, lps, n_is, ref_var):
+    """The selection arithmetic of ``exe_flow_matching.py:283,289-295`` on given solves: importance weights of the current state
+    (``u0``, ``vol0``: its pull-back) and of the ``n_is`` flow samples per chain (``refs``, ``xs``, ``vols``, ``lps``: [B n_is, ...]),
+    the categorical draw with ``split(keys[b], 4)[3]`` and the state update.  float64 on whatever arrays it is handed; the weights
+    are NOT stabilised (as in the reference), so they may vanish, overflow or be NaN: ``searchsorted`` then orders NaN last and
+    equal to itself.  Returns ``(state, info, stats)``, ``stats = dict(norm, choice)``."""
+    B = prev.position.shape[0]
+    ref = IndepGaussian(prev.position.shape[1], var=ref_var)
     kk = prng.split_rows(keys, 4)                      # :281 key_sample, key_hutch_prev, key_hutch, key_choice
-    o = dict(hutch=args.hutchs, rtol=args.rtol, atol=args.atol, mxstep=args.mxstep, n_ts=args.n_ts, fixed=fixed_mode(args))
-    u0, vol0 = ode.inverse_and_logdet(model, params, kk[:, 1], prev.position, **o)                 # :282
     with np.errstate(over="ignore", invalid="ignore"):
         w_prev = np.exp(prev.logdensity - ref.logprob(u0) - vol0)                                  # :283
-    ks = np.stack([prng.split(kk[b, 0], n_is) for b in range(B)]).reshape(B * n_is, 2)           # :284
-    kh = np.stack([prng.split(kk[b, 2], n_is) for b in range(B)]).reshape(B * n_is, 2)           # :286
-    refs = ref.sample_model_rows(ks)                                                               # :285
-    xs, vols = ode.transform_and_logdet(model, params, kh, refs, **o)                              # :287
-    lps, _ = value_and_grad(xs)                                                                    # :288
     with np.errstate(over="ignore", invalid="ignore"):
         w = np.exp(lps - ref.logprob(refs) - vols).reshape(B, n_is)                                # :289
     allw = np.concatenate([w_prev[:, None], w], axis=1)
@@ -108,8 +103,27 @@ def cis_step(keys, prev, value_and_grad, model, params, args, stats=None):
     wsel = norm[np.arange(B), choice]
     state = MALAState(np.where(m, xs[pick], prev.position), np.where(acc, lps[pick], prev.logdensity), prev.logdensity_grad)   # :293-295
     info = MALAInfo(wsel, acc, np.where(m, xs[pick], prev.position), wsel)
+    return state, info, dict(norm=norm, choice=choice)
+
+
+def cis_step(keys, prev, value_and_grad, model, params, args, stats=None):
+    """``exe_flow_matching.py:280-296``: conditional importance sampling with ``args.num_importance_samples`` fresh
+    flow samples per chain.  Quirk kept: an accepted state carries the STALE ``prev_state.logdensity_grad`` (``:295``)."""
+    B, d = prev.position.shape
+    n_is = int(args.num_importance_samples)
+    ref_var = REF_VARS[getattr(args, "ref_dist", "stdgauss")]
+    ref = IndepGaussian(d, var=ref_var)
+    kk = prng.split_rows(keys, 4)                      # :281 key_sample, key_hutch_prev, key_hutch, key_choice
+    o = dict(hutch=args.hutchs, rtol=args.rtol, atol=args.atol, mxstep=args.mxstep, n_ts=args.n_ts, fixed=fixed_mode(args))
+    u0, vol0 = ode.inverse_and_logdet(model, params, kk[:, 1], prev.position, **o)                 # :282
+    ks = np.stack([prng.split(kk[b, 0], n_is) for b in range(B)]).reshape(B * n_is, 2)           # :284
+    kh = np.stack([prng.split(kk[b, 2], n_is) for b in range(B)]).reshape(B * n_is, 2)           # :286
+    refs = ref.sample_model_rows(ks)                                                               # :285
+    xs, vols = ode.transform_and_logdet(model, params, kh, refs, **o)                              # :287
+    lps, _ = value_and_grad(xs)                                                                    # :288
+    state, info, sel = cis_select(keys, prev, u0, vol0, refs, xs, vols, lps, n_is, ref_var)       # :283, :289-295
     if stats is not None:
-        stats.update(u0=u0, vol0=vol0, refs=refs, xs=xs, vols=vols, lps=lps, norm=norm, choice=choice)
+        stats.update(u0=u0, vol0=vol0, refs=refs, xs=xs, vols=vols, lps=lps, **sel)
     return state, info
 
 
