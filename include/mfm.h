@@ -138,6 +138,23 @@ int mfm_mala_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double
                        float* d_pos, double* d_logp, float* d_grad,
                        float* d_acceptance_rate, uint8_t* d_is_accepted, float* d_proposed_position,
                        float* d_proposed_weight);
+/* n_steps steps of the same kernel in ONE call -- the scan of inference_loop0 (mcmc_utils.py:11-25) and the host loop of
+ * tempered.py:126-137.  phi-four and mixture targets: one launch, the chain stays in registers between the steps, bit-identical
+ * with n_steps single-step calls; the Cox process: n_steps launches of its step back to back on the context's stream, keys
+ * derived on the device.  Draws are always made in line (prefetched draws are not consulted).
+ * key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_mala_step uses its key; d_keys is ignored.
+ * key_mode 1 (chain-major): d_keys is uint32[n_chain_local][2]; step j of chain b uses split(d_keys[b], n_steps)[j] as
+ *   mfm_mala_step_keys uses a chain's key; key0 / key1 are ignored.
+ * State is updated in place.  Optional outputs (NULL to skip): d_n_accepted int32[B], accepted steps; d_acc_sum double[B], sum
+ * of the acceptance probabilities; the MALAInfo arrays of the LAST step; with thin >= 1 (n_steps % thin == 0, at least one of
+ * the two pointers) the state after every step j with (j + 1) % thin == 0: d_traj_pos float[n_steps / thin][B][dim],
+ * d_traj_logp double[n_steps / thin][B].  thin == 0 keeps no trajectory. */
+int mfm_mala_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                 double beta, double step_size, int textbook, int32_t n_steps, int32_t thin,
+                 float* d_pos, double* d_logp, float* d_grad,
+                 int32_t* d_n_accepted, double* d_acc_sum,
+                 float* d_acceptance_rate, uint8_t* d_is_accepted, float* d_proposed_position, float* d_proposed_weight,
+                 float* d_traj_pos, double* d_traj_logp);
 /* BUILD-SIDE MODE, not on the reference's MFM path (BASELINE.json's north star names a "MALA/HMC" step; the reference's loop uses
  * MALA only and vendors no hmc.py: SURVEY.md note 7): one Hamiltonian Monte Carlo step of every local chain as in blackjax's hmc
  * kernel (oracle/hmc.py restates it): momentum ~ N(0, I) from split(key, n_chain_total)[chain_offset + b] -> split(., 2)[0],

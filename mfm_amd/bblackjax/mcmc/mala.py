@@ -9,7 +9,9 @@ Same names and argument meaning as the reference (``MALAState`` / ``MALAInfo`` `
 * ``logdensity_fn`` must be built from ``dist.loglik / dist.logprior / dist.logprob`` of one of the built targets
   (``mfm_amd.distributions``); arbitrary closures raise ``NotImplementedError`` (no CPU fallback);
 * ``logdensity`` is float64, positions and gradients float32;
-* a caller that vmaps over its OWN keys (``bblackjax/smc/base.py:122-123``) passes ``rng_key`` of shape ``[n_chain, 2]``.
+* a caller that vmaps over its OWN keys (``bblackjax/smc/base.py:122-123``) passes ``rng_key`` of shape ``[n_chain, 2]``;
+* the kernel carries ``kernel.run(rng_key, state, logdensity_fn, step_size, num_steps, thin=0)``: ``num_steps`` steps in ONE
+  library call (``mfm_mala_run``), the scan of ``mcmc_utils.py:11-25`` with the chain resident on the device between steps.
 
 The acceptance rule is the reference's AS WRITTEN.  ``build_kernel(textbook=True)`` flips it.
 """
@@ -20,7 +22,7 @@ import numpy as np
 from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 
-__all__ = ["MALAState", "MALAInfo", "init", "build_kernel", "mala"]
+__all__ = ["MALAState", "MALAInfo", "MALARunInfo", "init", "build_kernel", "mala"]
 
 
 class MALAState(NamedTuple):
@@ -34,6 +36,17 @@ class MALAInfo(NamedTuple):
     is_accepted: object
     proposed_position: object
     proposed_weight: object
+
+
+class MALARunInfo(NamedTuple):
+    """What ``kernel.run`` reports: per chain the mean acceptance probability and the number of accepted steps, the LAST step's
+    ``MALAInfo``, and (with ``thin``) the kept states ``positions [num_steps / thin, n_chain, dim]`` /
+    ``logdensities [num_steps / thin, n_chain]`` (``None`` without)."""
+    acceptance_rate: object
+    num_accepted: object
+    last: MALAInfo
+    positions: object
+    logdensities: object
 
 
 def _engine(dist):
@@ -91,6 +104,36 @@ def build_kernel(textbook: bool = False):
             return MALAState(pos[0], logp[0], grad[0]), MALAInfo(acc[0], isacc.bool()[0], prop[0], w[0])
         return MALAState(pos, logp, grad), MALAInfo(acc, isacc.bool(), prop, w)
 
+    def run(rng_key, state: MALAState, logdensity_fn: Callable, step_size: float, num_steps: int, thin: int = 0):
+        """``num_steps`` calls of ``kernel`` in one: with ONE key step j uses ``split(rng_key, num_steps)[j]`` (the scan of
+        ``inference_loop0``, ``mcmc_utils.py:11-25``); with keys ``[n_chain_local, 2]`` step j of chain b uses
+        ``split(rng_key[b], num_steps)[j]`` (``smc/tempered.py:126-137``).  Bit-identical with that loop.  ``thin >= 1`` keeps
+        the state after every ``thin``-th step."""
+        dist, beta = resolve_logdensity(logdensity_fn)
+        eng = _engine(dist)
+        t = eng.torch
+        if state.position.ndim == 1:
+            raise NotImplementedError("kernel.run takes the batched state [n_chain_local, dim]; loop over kernel() for a single chain")
+        num_steps, thin = int(num_steps), int(thin)
+        pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()
+        n, dev = pos.shape[0], pos.device
+        n_acc = t.empty(n, device=dev, dtype=t.int32)
+        acc_sum = t.empty(n, device=dev, dtype=t.float64)
+        acc = t.empty(n, device=dev, dtype=t.float32)
+        isacc = t.empty(n, device=dev, dtype=t.uint8)
+        prop = t.empty_like(pos)
+        w = t.empty(n, device=dev, dtype=t.float32)
+        traj_pos = traj_logp = None
+        if thin > 0 and num_steps >= thin and num_steps % thin == 0:       # (anything else: the library names the bad argument)
+            traj_pos = t.empty((num_steps // thin,) + tuple(pos.shape), device=dev, dtype=t.float32)
+            traj_logp = t.empty((num_steps // thin, n), device=dev, dtype=t.float64)
+        if getattr(rng_key, "ndim", 1) == 2 and not t.is_tensor(rng_key):
+            rng_key = t.as_tensor(np.ascontiguousarray(rng_key, dtype=np.uint32).view(np.int32), device=dev)
+        eng.ctx.mala_run(rng_key, beta, step_size, num_steps, pos, logp, grad, thin=thin, n_acc=n_acc, acc_sum=acc_sum, acc=acc,
+                         is_acc=isacc, proposed=prop, weight=w, traj_pos=traj_pos, traj_logp=traj_logp, textbook=textbook)
+        return MALAState(pos, logp, grad), MALARunInfo(acc_sum / num_steps, n_acc, MALAInfo(acc, isacc.bool(), prop, w), traj_pos, traj_logp)
+
+    kernel.run = run
     return kernel
 
 
@@ -109,4 +152,8 @@ class mala:
         def step_fn(rng_key, state):
             return kernel(rng_key, state, logdensity_fn, step_size)
 
+        def run_fn(rng_key, state, num_steps, thin=0):
+            return kernel.run(rng_key, state, logdensity_fn, step_size, num_steps, thin)
+
+        step_fn.run = run_fn
         return SamplingAlgorithm(init_fn, step_fn)

@@ -1,7 +1,12 @@
 """``bblackjax/smc/tempered.py``: tempered SMC kernel (``:27-148``) on the device MALA kernels.
 
 The MCMC move targets ``logprior + state.lmbda * loglikelihood`` -- the temperature BEFORE the increment, as the reference
-writes it (``:120-123``) -- and the particles are weighed with ``delta * loglikelihood`` (``:118-119``)."""
+writes it (``:120-123``) -- and the particles are weighed with ``delta * loglikelihood`` (``:118-119``).
+
+An MCMC kernel that carries ``.run`` (``mcmc/mala.py``) moves the particles with ONE library call per temperature
+(``mfm_mala_run``, chain-major keys) instead of ``num_mcmc_steps`` calls from the loop below: the same keys, the same bits.
+``MFM_SMC_STEPWISE=1`` in the environment keeps the loop."""
+import os
 from typing import NamedTuple
 
 from ... import random as jr
@@ -33,6 +38,9 @@ def build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resa
 
         def mcmc_kernel(keys, particles):                                               # :126-137, batched over particles
             st = mcmc_init_fn(particles, tempered_logposterior_fn)
+            if num_mcmc_steps >= 1 and hasattr(mcmc_step_fn, "run") and os.environ.get("MFM_SMC_STEPWISE", "0") != "1":
+                st, run_info = mcmc_step_fn.run(keys, st, tempered_logposterior_fn, num_steps=num_mcmc_steps, **mcmc_parameters)
+                return st.position, run_info.last
             info = None
             step_keys = jr.split_rows(keys, num_mcmc_steps)                             # [N, steps, 2]
             for j in range(num_mcmc_steps):

@@ -12,6 +12,7 @@
 #include <rccl/rccl.h>     // types and enums only: the library is resolved at run time (rccl_api), never linked
 
 #include "mala.hip"
+#include "mala_run.hip"
 #include "lgcp.hip"
 #include "hmc.hip"
 #include "fm.hip"
@@ -98,6 +99,7 @@ struct mfm_ctx {
   Switches sw;                           // the A/B switches as read at mfm_create: installed by every entry point (use_ctx)
   FmMala fuse_mala = {};                 // on != 0 during a mfm_train_iter whose MALA step rides in the training kernel
   int opt_resident_wgs = 0;              // workgroups of reduce_adamw_kernel this device holds at once (occupancy query at create)
+  void* run_ws = nullptr; size_t run_ws_cap = 0;   // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
 };
 
 // The development switches (common.hip.h) are read once per mfm_create and belong to THAT context: every entry point installs its
@@ -390,7 +392,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf};
+                x->d_att, x->att_buf, x->run_ws};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -611,6 +613,76 @@ extern "C" int mfm_mala_step_keys(mfm_ctx* x, const uint32_t* d_keys, double bet
                                   double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc, float* d_prop, float* d_pw) { use_ctx(x);
   if (!d_keys) return fail(MFM_EINVAL, "null key array");
   return mala_step_common(x, 0, 0, d_keys, beta, step, textbook, d_pos, d_logp, d_grad, d_acc, d_isacc, d_prop, d_pw);
+}
+
+// n_steps MALA steps in one call (mala_run.hip): the chain stays in registers between the steps.  The Cox process, whose step is the
+// 16-chain tile of lgcp.hip, gets n_steps launches of that step back to back on the context's stream instead (keys and tallies on the device).
+extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int textbook,
+                            int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum,
+                            float* d_acc, uint8_t* d_isacc, float* d_prop, float* d_pw, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
+  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
+  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
+  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
+  if (thin < 0) return fail(MFM_EINVAL, "thin must not be negative (got %d)", thin);
+  if (thin > 0 && n_steps % thin) return fail(MFM_EINVAL, "thin (%d) must divide n_steps (%d)", thin, n_steps);
+  if (thin > 0 && !d_traj_pos && !d_traj_logp) return fail(MFM_EINVAL, "thin > 0 needs d_traj_pos or d_traj_logp");
+  const int B = x->cfg.n_chain_local, d = x->cfg.dim;
+  if (x->net.T.kind == MFM_TARGET_LGCP) {
+    // workspace: keys uint32 [B][2] | acc_prob float [B] | accepted uint8 [B]
+    const size_t need = (size_t)B * (8 + 4 + 1);
+    if (x->run_ws_cap < need) {
+      if (x->run_ws) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(x->run_ws); x->run_ws = nullptr; x->run_ws_cap = 0; }
+      HIPCHK(hipMalloc(&x->run_ws, need));
+      x->run_ws_cap = need;
+    }
+    uint32_t* ws_keys = (uint32_t*)x->run_ws;
+    float* ws_acc = d_acc ? d_acc : (float*)((char*)x->run_ws + (size_t)B * 8);
+    uint8_t* ws_isacc = d_isacc ? d_isacc : (uint8_t*)((char*)x->run_ws + (size_t)B * 12);
+    const bool tally = d_n_acc || d_acc_sum;
+    if (d_n_acc) HIPCHK(hipMemsetAsync(d_n_acc, 0, (size_t)B * sizeof(int32_t), x->stream));
+    if (d_acc_sum) HIPCHK(hipMemsetAsync(d_acc_sum, 0, (size_t)B * sizeof(double), x->stream));
+    LgcpArgs l; memset(&l, 0, sizeof l);
+    l.T = x->net.T; l.dp = x->net.dp; l.mode = 1; l.keys = ws_keys; l.n_total = x->cfg.n_chain_total;
+    l.chain_offset = x->cfg.chain_offset; l.B = B; l.beta = beta; l.eps = step; l.textbook = textbook;
+    l.pos = d_pos; l.logp = d_logp; l.grad = d_grad;
+    ProfScope ps_(x, PROF_MALA);
+    const dim3 kgrid((B + 255) / 256), kblock(256);
+    for (int s = 0; s < n_steps; ++s) {
+      const bool last = s == n_steps - 1;
+      hipLaunchKernelGGL(mala_run_keys_kernel, kgrid, kblock, 0, x->stream, key_mode, Key2{k0, k1}, d_keys, (uint32_t)n_steps, (uint32_t)s,
+                         (uint32_t)x->cfg.n_chain_total, (uint32_t)x->cfg.chain_offset, B, ws_keys);
+      l.acc_prob = (tally || (last && d_acc)) ? ws_acc : nullptr;        // (the caller's buffers where given: the last step leaves its info there)
+      l.accepted = (tally || (last && d_isacc)) ? ws_isacc : nullptr;
+      l.proposed = last ? d_prop : nullptr; l.prop_weight = last ? d_pw : nullptr;
+      if (lgcp_mala_dispatch(x, l)) return fail(MFM_ETOOLARGE, "dim %d too large for the LGCP MALA kernel", d);
+      if (tally) hipLaunchKernelGGL(mala_run_tally_kernel, kgrid, kblock, 0, x->stream, B, ws_acc, ws_isacc, d_n_acc, d_acc_sum);
+      LAUNCHCHK();
+      if (thin > 0 && (s + 1) % thin == 0) {
+        const size_t snap = (size_t)((s + 1) / thin - 1);
+        if (d_traj_pos) HIPCHK(hipMemcpyAsync(d_traj_pos + snap * (size_t)B * d, d_pos, (size_t)B * d * sizeof(float), hipMemcpyDeviceToDevice, x->stream));
+        if (d_traj_logp) HIPCHK(hipMemcpyAsync(d_traj_logp + snap * (size_t)B, d_logp, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+      }
+    }
+    x->ctr[CTR_MALA] += (int64_t)B * n_steps; x->ctr[CTR_MALA_BYTES] += (int64_t)B * n_steps * 4 * (5 * d + 5);
+    return MFM_OK;
+  }
+  MalaRunArgs r; memset(&r, 0, sizeof r);
+  r.m = mala_args(x, beta);
+  r.m.key = Key2{k0, k1}; r.m.keys = key_mode == 1 ? d_keys : nullptr; r.m.eps = step; r.m.textbook = textbook;
+  r.m.pos = d_pos; r.m.logp = d_logp; r.m.grad = d_grad;
+  r.m.acc_prob = d_acc; r.m.accepted = d_isacc; r.m.proposed = d_prop; r.m.prop_weight = d_pw;
+  r.key_mode = key_mode; r.n_steps = n_steps; r.thin = thin;
+  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum; r.traj_pos = d_traj_pos; r.traj_logp = d_traj_logp;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_mala_run(r, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large for the MALA kernel", d);
+  LAUNCHCHK();
+  // state in and out once, the trajectory rows that were kept
+  x->ctr[CTR_MALA] += (int64_t)B * n_steps;
+  x->ctr[CTR_MALA_BYTES] += (int64_t)B * 4 * (4 * d + 4) + (thin > 0 ? (int64_t)(n_steps / thin) * B * (4 * (d_traj_pos ? d : 0) + (d_traj_logp ? 8 : 0)) : 0);
+  return MFM_OK;
 }
 
 // Build-side mode (hmc.hip; not on the reference's MFM path): one HMC step of every local chain, state updated in place like mfm_mala_step
