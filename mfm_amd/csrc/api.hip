@@ -533,6 +533,14 @@ static MalaArgs mala_args(mfm_ctx* x, double beta) {
   a.beta = beta;
   return a;
 }
+static LgcpArgs lgcp_args(mfm_ctx* x, int mode, double beta, double eps) {      // mode 0: init (eps unused, any positive value), 1: step
+  LgcpArgs l; memset(&l, 0, sizeof l);
+  l.T = x->net.T; l.dp = x->net.dp; l.mode = mode; l.n_total = x->cfg.n_chain_total; l.chain_offset = x->cfg.chain_offset; l.B = x->cfg.n_chain_local;
+  l.beta = beta; l.eps = eps;
+  return l;
+}
+static void count_mala_steps(mfm_ctx* x, int64_t n) { x->ctr[CTR_MALA] += n; x->ctr[CTR_MALA_BYTES] += n * 4 * (5 * x->cfg.dim + 5); }   // n single chain steps
+static int too_large(mfm_ctx* x, const char* kernel) { return fail(MFM_ETOOLARGE, "dim %d too large for the %s kernel", x->cfg.dim, kernel); }
 
 // LGCP dimensions beyond the fused tile kernel (d > 1024) go through the wide family's propose / K^-1 GEMM / accept split
 static int wide_mala_lgcp(mfm_ctx* x, const LgcpArgs& l) {
@@ -557,16 +565,14 @@ extern "C" int mfm_mala_init(mfm_ctx* x, const float* d_pos, double beta, double
   NEED_TARGET();
   if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
   if (x->net.T.kind == MFM_TARGET_LGCP) {
-    LgcpArgs l; memset(&l, 0, sizeof l);
-    l.T = x->net.T; l.dp = x->net.dp; l.mode = 0; l.n_total = x->cfg.n_chain_total; l.chain_offset = x->cfg.chain_offset;
-    l.B = x->cfg.n_chain_local; l.beta = beta; l.eps = 1.0; l.pos = const_cast<float*>(d_pos); l.logp = d_logp; l.grad = d_grad;
-    if (lgcp_mala_dispatch(x, l)) return fail(MFM_ETOOLARGE, "dim %d too large for the LGCP MALA kernel", x->cfg.dim);
-    LAUNCHCHK();
-    return MFM_OK;
+    LgcpArgs l = lgcp_args(x, 0, beta, 1.0);
+    l.pos = const_cast<float*>(d_pos); l.logp = d_logp; l.grad = d_grad;
+    if (lgcp_mala_dispatch(x, l)) return too_large(x, "LGCP MALA");
+  } else {
+    MalaArgs a = mala_args(x, beta);
+    a.pos = const_cast<float*>(d_pos); a.logp = d_logp; a.grad = d_grad;
+    if (launch_mala_init(a, x->stream)) return too_large(x, "MALA");
   }
-  MalaArgs a = mala_args(x, beta);
-  a.pos = const_cast<float*>(d_pos); a.logp = d_logp; a.grad = d_grad;
-  if (launch_mala_init(a, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large for the MALA kernel", x->cfg.dim);
   LAUNCHCHK();
   return MFM_OK;
 }
@@ -577,14 +583,13 @@ static int mala_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t
   if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
   if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
   if (x->net.T.kind == MFM_TARGET_LGCP) {
-    LgcpArgs l; memset(&l, 0, sizeof l);
-    l.T = x->net.T; l.dp = x->net.dp; l.mode = 1; l.key = Key2{k0, k1}; l.keys = d_keys; l.n_total = x->cfg.n_chain_total;
-    l.chain_offset = x->cfg.chain_offset; l.B = x->cfg.n_chain_local; l.beta = beta; l.eps = step; l.textbook = textbook;
+    LgcpArgs l = lgcp_args(x, 1, beta, step);
+    l.key = Key2{k0, k1}; l.keys = d_keys; l.textbook = textbook;
     l.pos = d_pos; l.logp = d_logp; l.grad = d_grad; l.acc_prob = d_acc; l.accepted = d_isacc; l.proposed = d_prop; l.prop_weight = d_pw;
     ProfScope ps_(x, PROF_MALA);
-    if (lgcp_mala_dispatch(x, l)) return fail(MFM_ETOOLARGE, "dim %d too large for the LGCP MALA kernel", x->cfg.dim);
+    if (lgcp_mala_dispatch(x, l)) return too_large(x, "LGCP MALA");
     LAUNCHCHK();
-    x->ctr[CTR_MALA] += x->cfg.n_chain_local; x->ctr[CTR_MALA_BYTES] += (int64_t)x->cfg.n_chain_local * 4 * (5 * x->cfg.dim + 5);
+    count_mala_steps(x, x->cfg.n_chain_local);
     return MFM_OK;
   }
   MalaArgs a = mala_args(x, beta);
@@ -599,9 +604,9 @@ static int mala_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t
   a.pos = d_pos; a.logp = d_logp; a.grad = d_grad;
   a.acc_prob = d_acc; a.accepted = d_isacc; a.proposed = d_prop; a.prop_weight = d_pw;
   ProfScope ps_(x, PROF_MALA);
-  if (launch_mala_step(a, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large for the MALA kernel", x->cfg.dim);
+  if (launch_mala_step(a, x->stream)) return too_large(x, "MALA");
   LAUNCHCHK();
-  x->ctr[CTR_MALA] += x->cfg.n_chain_local; x->ctr[CTR_MALA_BYTES] += (int64_t)x->cfg.n_chain_local * 4 * (5 * x->cfg.dim + 5);
+  count_mala_steps(x, x->cfg.n_chain_local);
   return MFM_OK;
 }
 
@@ -644,9 +649,8 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
     const bool tally = d_n_acc || d_acc_sum;
     if (d_n_acc) HIPCHK(hipMemsetAsync(d_n_acc, 0, (size_t)B * sizeof(int32_t), x->stream));
     if (d_acc_sum) HIPCHK(hipMemsetAsync(d_acc_sum, 0, (size_t)B * sizeof(double), x->stream));
-    LgcpArgs l; memset(&l, 0, sizeof l);
-    l.T = x->net.T; l.dp = x->net.dp; l.mode = 1; l.keys = ws_keys; l.n_total = x->cfg.n_chain_total;
-    l.chain_offset = x->cfg.chain_offset; l.B = B; l.beta = beta; l.eps = step; l.textbook = textbook;
+    LgcpArgs l = lgcp_args(x, 1, beta, step);
+    l.keys = ws_keys; l.textbook = textbook;
     l.pos = d_pos; l.logp = d_logp; l.grad = d_grad;
     ProfScope ps_(x, PROF_MALA);
     const dim3 kgrid((B + 255) / 256), kblock(256);
@@ -657,7 +661,7 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
       l.acc_prob = (tally || (last && d_acc)) ? ws_acc : nullptr;        // (the caller's buffers where given: the last step leaves its info there)
       l.accepted = (tally || (last && d_isacc)) ? ws_isacc : nullptr;
       l.proposed = last ? d_prop : nullptr; l.prop_weight = last ? d_pw : nullptr;
-      if (lgcp_mala_dispatch(x, l)) return fail(MFM_ETOOLARGE, "dim %d too large for the LGCP MALA kernel", d);
+      if (lgcp_mala_dispatch(x, l)) return too_large(x, "LGCP MALA");
       if (tally) hipLaunchKernelGGL(mala_run_tally_kernel, kgrid, kblock, 0, x->stream, B, ws_acc, ws_isacc, d_n_acc, d_acc_sum);
       LAUNCHCHK();
       if (thin > 0 && (s + 1) % thin == 0) {
@@ -666,7 +670,7 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
         if (d_traj_logp) HIPCHK(hipMemcpyAsync(d_traj_logp + snap * (size_t)B, d_logp, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, x->stream));
       }
     }
-    x->ctr[CTR_MALA] += (int64_t)B * n_steps; x->ctr[CTR_MALA_BYTES] += (int64_t)B * n_steps * 4 * (5 * d + 5);
+    count_mala_steps(x, (int64_t)B * n_steps);
     return MFM_OK;
   }
   MalaRunArgs r; memset(&r, 0, sizeof r);
@@ -677,7 +681,7 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
   r.key_mode = key_mode; r.n_steps = n_steps; r.thin = thin;
   r.n_acc = d_n_acc; r.acc_sum = d_acc_sum; r.traj_pos = d_traj_pos; r.traj_logp = d_traj_logp;
   ProfScope ps_(x, PROF_MALA);
-  if (launch_mala_run(r, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large for the MALA kernel", d);
+  if (launch_mala_run(r, x->stream)) return too_large(x, "MALA");
   LAUNCHCHK();
   // state in and out once, the trajectory rows that were kept
   x->ctr[CTR_MALA] += (int64_t)B * n_steps;
@@ -698,7 +702,7 @@ extern "C" int mfm_hmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, d
   a.num_steps = num_steps; a.beta = beta; a.eps = step;
   a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.acc_prob = d_acc; a.accepted = d_isacc;
   ProfScope ps_(x, PROF_MALA);
-  if (launch_hmc_step(a, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large for the HMC kernel", x->cfg.dim);
+  if (launch_hmc_step(a, x->stream)) return too_large(x, "HMC");
   LAUNCHCHK();
   x->ctr[CTR_MALA] += x->cfg.n_chain_local;
   return MFM_OK;

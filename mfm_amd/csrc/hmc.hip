@@ -2,13 +2,13 @@
 // "MALA/HMC log-density-and-grad step", the reference's MFM loop has MALA only and vendors no hmc.py (SURVEY.md note 7).  The kernel
 // follows blackjax's HMC (the package the reference's bblackjax was cut from), restated in oracle/hmc.py: momentum ~ N(0, I) from
 // split(key, 2)[0], num_steps velocity-Verlet steps (half kick, drift, value-and-gradient, half kick), H = -logp + |p|^2 / 2,
-// accept with min(1, exp(H_0 - H_end)) against uniform(split(key, 2)[1]) (proposal.py:105,178-179).
+// accept with min(1, exp(H_0 - H_end)) against uniform(split(key, 2)[1]) (the accept rule's tail: mcmc.hip.h).
 // Layout as the MALA kernel (mala.hip): positions / gradients float32, log-density float64; the momentum lives in float64 registers,
 // the trajectory's position is rounded to float32 after every drift (it is what the target is evaluated at); energies are summed in
 // float64 over the wave.  Targets: phi-four and the Gaussian mixtures (row_value_grad); the Cox process needs the K^-1 GEMM tile
 // (lgcp.hip) and is not served.
 #pragma once
-// (included by api.hip after mala.hip: MalaArgs' helpers row_value_grad, MALA_DISPATCH, mala_smem)
+// (included by api.hip after mala.hip: mcmc.hip.h, MalaArgs' helpers row_value_grad, MALA_DISPATCH, mala_smem)
 
 struct HmcArgs {
   TargetDev T;
@@ -31,8 +31,8 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
   float* xs = smem + wave * rowlen + 1;
   float* gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
   const size_t row = (size_t)b * d;
-  const Key2 kb = split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b);
-  const Key2 k_mom = split_at(kb, 2, 0), k_acc = split_at(kb, 2, 1);
+  const Key2 kb = mcmc_chain_key(a.key, nullptr, a.n_total, a.chain_offset, b);
+  const Key2 k_mom = mcmc_step_key(kb, MCMC_K_INT), k_acc = mcmc_step_key(kb, MCMC_K_RMH);
   float x0[MAXIT], g0[MAXIT], x[MAXIT], g[MAXIT];
   double p[MAXIT];
   double kin = 0.0;
@@ -76,10 +76,8 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) kin1 += (lane + 64 * it < d) ? p[it] * p[it] : 0.0;
   const double h1 = -lp + 0.5 * wave_sum(kin1);
-  double delta = h0 - h1;
-  if (isnan(delta)) delta = -INFINITY;                                      // proposal.py:105
-  const double pa = fmin(exp(delta), 1.0);                                  // proposal.py:178
-  const bool acc = uniform01(k_acc, 0, 1) < pa;                             // proposal.py:179
+  const double pa = mala_accept_p(h0 - h1);
+  const bool acc = uniform01(k_acc, 0, 1) < pa;
   if (acc) {
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {

@@ -5,9 +5,9 @@
 //   loglik(x)   = sum_i (x_i c_i - a exp(x_i))                      a = 1/d              (cox_process_utils.py:113-115)
 //   logprior(x) = -1/2 (x - mu)^T K^-1 (x - mu) + log_norm                              (distributions.py:299-303)
 //   grad        = beta (c - a exp(x)) - K^-1 (x - mu)
-// mode 0: mala_init (value and gradient at the given positions); 1: one MALA step (mala.py:86-118, as written).
+// mode 0: mala_init (value and gradient at the given positions); 1: one MALA step.  Element arithmetic: mcmc.hip.h, fused form.
 #include "mlp.hip.h"
-#include "prng.hip.h"
+#include "mcmc.hip.h"
 
 #define LGCP_NW 8
 
@@ -33,13 +33,12 @@ __global__ __launch_bounds__(LGCP_NW * 64) void mala_lgcp_kernel(LgcpArgs a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int bi = b0 + 4 * g + i;
-    const Key2 kb = a.keys ? Key2{a.keys[2 * bi], a.keys[2 * bi + 1]} : split_at(a.key, a.n_total, a.chain_offset + (uint32_t)bi);     // exe_flow_matching.py:303
-    k_int[i] = split_at(kb, 2, 0);                                                                // mala.py:93
+    k_int[i] = mcmc_step_key(mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, bi), MCMC_K_INT);
   }
   double lp_old[4];        // read BEFORE any wave can publish an accepted log-density for the same chain
 #pragma unroll
   for (int i = 0; i < 4; ++i) lp_old[i] = a.mode == 1 ? a.logp[b0 + 4 * g + i] : 0.0;
-  const double s2e = sqrt(2.0 * a.eps);
+  const double s2e = mala_s2e(a.eps);
 #pragma unroll
   for (int q = 0; q < TPW; ++q) {
     const int col = (wave + LGCP_NW * q) * 16 + c;
@@ -52,9 +51,7 @@ __global__ __launch_bounds__(LGCP_NW * 64) void mala_lgcp_kernel(LgcpArgs a) {
         x[q][i] = a.pos[o];
         if (a.mode == 1) {
           gr[q][i] = a.grad[o];
-          const double th = s2e * normal64(k_int[i], (uint32_t)col, (uint32_t)d);                 // util.py:80-82
-          th1[i] += th * th;
-          xn[q][i] = (float)((double)x[q][i] + a.eps * (double)gr[q][i] + th);                    // diffusions.py:25-30
+          xn[q][i] = mala_propose<true>(x[q][i], gr[q][i], normal64(k_int[i], (uint32_t)col, (uint32_t)d), a.eps, s2e, th1[i]);
         } else {
           xn[q][i] = x[q][i];
         }
@@ -78,11 +75,9 @@ __global__ __launch_bounds__(LGCP_NW * 64) void mala_lgcp_kernel(LgcpArgs a) {
                                 if (col < d) {
                                   const float y = acc[i] + kb;
                                   const float ex = expf(xv);
-                                  gv = (float)a.beta * (a.T.counts[col] - a.T.poisson_a * ex) - y;
-                                  lik[i] += (double)xv * (double)a.T.counts[col] - (double)a.T.poisson_a * (double)ex;
-                                  quad[i] += (double)(xv - a.T.mu) * (double)y;
-                                  const double t = (double)xo - (double)xv - a.eps * (double)gv;
-                                  th2[i] += t * t;
+                                  gv = cox_grad(a.T, a.beta, col, ex, y);
+                                  cox_terms(a.T, col, xv, ex, y, lik[i], quad[i]);
+                                  mala_back<true>(xo, xv, gv, a.eps, th2[i]);
                                 }
 #pragma unroll
                                 for (int qq = 0; qq < TPW; ++qq)
@@ -124,21 +119,15 @@ __global__ __launch_bounds__(LGCP_NW * 64) void mala_lgcp_kernel(LgcpArgs a) {
       sl += red[(0 * LGCP_NW + w) * 16 + row]; sq += red[(1 * LGCP_NW + w) * 16 + row];
       s2 += red[(2 * LGCP_NW + w) * 16 + row]; s1 += red1[w * 16 + row];
     }
-    lpn[i] = a.beta * sl - 0.5 * sq + (double)a.T.log_norm;
+    lpn[i] = cox_logp(a.T, a.beta, sl, sq);
     acc[i] = true;
     if (a.mode == 1) {
-      const double lp = lp_old[i], inv4e = 0.25 / a.eps;
-      const double new_E = -lp + inv4e * s1, prev_E = -lpn[i] + inv4e * s2;          // mala.py:68-79, proposal.py:157-158
-      double delta = prev_E - new_E;                                                 // proposal.py:104
-      if (a.textbook) delta = -delta;
-      if (isnan(delta)) delta = -INFINITY;                                           // proposal.py:105
-      const double p = fmin(exp(delta), 1.0);                                        // proposal.py:178
-      const Key2 kb = a.keys ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b);
-      acc[i] = uniform01(split_at(kb, 2, 1), 0, 1) < p;                              // proposal.py:179
+      const double p = mala_accept_p<true>(lp_old[i], lpn[i], s1, s2, a.eps, a.textbook);
+      acc[i] = uniform01(mcmc_step_key(mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, b), MCMC_K_RMH), 0, 1) < p;
       if (wave == 0 && c == 0) {
         if (a.acc_prob) a.acc_prob[b] = (float)p;
         if (a.accepted) a.accepted[b] = acc[i] ? 1 : 0;
-        if (a.prop_weight) a.prop_weight[b] = (float)exp(lpn[i] + inv4e * s2);       // mala.py:104-113
+        if (a.prop_weight) a.prop_weight[b] = (float)mala_prop_weight(lpn[i], s2, a.eps);
       }
     }
     if (wave == 0 && c == 0 && acc[i]) a.logp[b] = lpn[i];

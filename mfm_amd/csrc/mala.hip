@@ -1,17 +1,14 @@
 // K1: fused MALA step over parallel chains (one wavefront per chain), K2: target value & gradient.
 //
-// Replaces the XLA computation of `jax.vmap(kernel)(keys, states)` at exe_flow_matching.py:313, i.e.
-// bblackjax/mcmc/mala.py:86-118 + diffusions.py:19-34 + proposal.py:104-112,157-159,178-186, and
-// `jax.vmap(init)` at exe_flow_matching.py:316 (mala.py:51-54).  The acceptance rule is reproduced AS WRITTEN
-// (p = min(1, exp(prev_E - new_E)), the inverse of the textbook ratio); `textbook` flips it.
+// Replaces the XLA computation of `jax.vmap(kernel)(keys, states)` at exe_flow_matching.py:313 (the step's arithmetic and its
+// citations: mcmc.hip.h) and `jax.vmap(init)` at exe_flow_matching.py:316 (mala.py:51-54).
 //
 // Layout: position / gradient [B, d] float32 row-major, logdensity [B] float64 (|logp| ~ 4e4 for phi-four at
 // d = 256, where a float32 ulp is 4e-3 -- too coarse for the energy difference).  One wave owns one chain: lanes
 // stride the row (coalesced 256 B per wave instruction), the proposal row is staged in LDS with one zero pad on
 // each side for the stencil, energies are reduced in float64 with wavefront shuffles.  Noise is drawn in-kernel
 // (threefry + float64 erfinv), so the only HBM traffic is the algorithmic 4*(5d+5) bytes per chain.
-#include "prng.hip.h"
-#include "targets.hip.h"
+#include "mcmc.hip.h"
 
 #define MALA_WAVES 4
 #define MALA_MAXD_SMALL 8
@@ -137,7 +134,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void loglik_kernel(MalaArgs a, dou
   if (lane == 0) out[b] = lp;
 }
 
-// One MALA step of the NCH chains b[0..NCH) by ONE wave (diffusions.py:19-34, mala.py:86-118, proposal.py:104-112,157-159,178-186).
+// One MALA step of the NCH chains b[0..NCH) by ONE wave (the step's arithmetic: mcmc.hip.h, strict form).
 // xs[c]: the wave's LDS row for chain c (d floats, zero pads at [-1] and [d] written here); on return it holds the chain's NEW
 // position (proposal if accepted, the old position otherwise), which the fused MALA + training kernel (fm.hip) reads instead of
 // going back to HBM.  The chains of a wave are independent: their loads and float64 butterfly sums interleave.  Only the wave's
@@ -151,15 +148,12 @@ struct MalaNoHook { __device__ __forceinline__ void operator()() const {} };
 template <int MAXIT, int NCH, typename Hook = MalaNoHook, bool BCRT = false>
 __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b)[NCH], float* const (&xs)[NCH], float* const (&gsm)[NCH], int lane,
                                                 Hook after_loads = Hook()) {
-  // No multiply-add contraction in this function's own arithmetic: it is instantiated in two kernels (stand-alone, and inside the
-  // training kernel where unused outputs fold away), and whether `-(beta * S) + c * t` becomes one fused operation depended on how
-  // many uses beta * S had left -- acceptance probabilities differed in the last bit between the two at beta < 1.
-#pragma clang fp contract(off)
+  // (strict form: with contraction, acceptance probabilities differed in the last bit between this function's two kernels at beta < 1)
   const int d = a.T.dim;
   float x[NCH][MAXIT], g[NCH][MAXIT], xn[NCH][MAXIT];
   double th1[NCH];                        // |x' - x - eps g|^2 = 2 eps |noise|^2
   Key2 k_int[NCH], k_rmh[NCH];
-  const double s2e = sqrt(2.0 * a.eps);
+  const double s2e = mala_s2e(a.eps);
   draw_t nz[NCH][MAXIT];                  // prefetched draws: all loads in flight before the first use
   double lp0[NCH], u0[NCH];               // the accept step's two scalars: requested here, a whole HBM round trip before their use
 #pragma unroll
@@ -170,9 +164,9 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
     u0[c] = a.pre_u ? a.pre_u[b[c]] : 0.0;
     if (lane == 0) { xs[c][-1] = 0.f; xs[c][d] = 0.f; }
     if (!a.pre_n) {
-      const Key2 kb = a.keys ? Key2{a.keys[2 * b[c]], a.keys[2 * b[c] + 1]} : split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b[c]);     // exe_flow_matching.py:303
-      k_int[c] = split_at(kb, 2, 0);                                                 // mala.py:93
-      k_rmh[c] = split_at(kb, 2, 1);
+      const Key2 kb = mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, b[c]);
+      k_int[c] = mcmc_step_key(kb, MCMC_K_INT);
+      k_rmh[c] = mcmc_step_key(kb, MCMC_K_RMH);
     } else {
 #pragma unroll
       for (int it = 0; it < MAXIT; ++it) { const int j = lane + 64 * it; nz[c][it] = j < d ? a.pre_n[row + j] : (draw_t)0; }
@@ -194,10 +188,8 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
     for (int it = 0; it < MAXIT; ++it) {
       const int j = lane + 64 * it;
       if (j < d) {
-        const double n = a.pre_n ? (double)nz[c][it] : (double)(draw_t)normal64(k_int[c], (uint32_t)j, (uint32_t)d);   // util.py:80-82
-        const double th = s2e * n;
-        th1[c] += th * th;
-        xn[c][it] = (float)((double)x[c][it] + a.eps * (double)g[c][it] + th);     // diffusions.py:25-30
+        const double n = a.pre_n ? (double)nz[c][it] : (double)(draw_t)normal64(k_int[c], (uint32_t)j, (uint32_t)d);
+        xn[c][it] = mala_propose<false>(x[c][it], g[c][it], n, a.eps, s2e, th1[c]);
         xs[c][j] = xn[c][it];
       }
     }
@@ -211,15 +203,12 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
   double lpn[NCH], th2[NCH];              // th2 = |x - x' - eps g'|^2
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
-    lpn[c] = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs[c], d, lane, gn[c], gsm[c]);    // diffusions.py:32
+    lpn[c] = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs[c], d, lane, gn[c], gsm[c]);
     th2[c] = 0.0;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
       const int j = lane + 64 * it;
-      if (j < d) {
-        const double t = (double)x[c][it] - (double)xn[c][it] - a.eps * (double)gn[c][it];
-        th2[c] += t * t;
-      }
+      if (j < d) mala_back<false>(x[c][it], xn[c][it], gn[c][it], a.eps, th2[c]);
     }
   }
   FM_STAMP(13);
@@ -229,16 +218,9 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const size_t row = (size_t)b[c] * d;
-    const double lp = lp0[c];
-    const double inv4e = 0.25 / a.eps;
-    const double new_E = -lp + inv4e * th1[c];                                       // mala.py:68-79, proposal.py:157
-    const double prev_E = -lpn[c] + inv4e * th2[c];                                  // proposal.py:158
-    double delta = prev_E - new_E;                                                   // proposal.py:104
-    if (a.textbook) delta = -delta;
-    if (isnan(delta)) delta = -INFINITY;                                             // proposal.py:105
-    const double p = fmin(exp(delta), 1.0);                                          // proposal.py:178
+    const double p = mala_accept_p<false>(lp0[c], lpn[c], th1[c], th2[c], a.eps, a.textbook);
     const double u = a.pre_u ? u0[c] : uniform01(k_rmh[c], 0, 1);
-    const bool acc = u < p;                                                          // proposal.py:179
+    const bool acc = u < p;
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
       const int j = lane + 64 * it;
@@ -252,7 +234,7 @@ __device__ __forceinline__ void mala_chain_step(const MalaArgs& a, const int (&b
       if (acc) a.logp[b[c]] = lpn[c];
       if (a.acc_prob) a.acc_prob[b[c]] = (float)p;
       if (a.accepted) a.accepted[b[c]] = acc ? 1 : 0;
-      if (a.prop_weight) a.prop_weight[b[c]] = (float)exp(lpn[c] + inv4e * th2[c]);   // mala.py:104-113 (diagnostic)
+      if (a.prop_weight) a.prop_weight[b[c]] = (float)mala_prop_weight(lpn[c], th2[c], a.eps);
     }
   }
 }

@@ -5,13 +5,11 @@
 // wave's own LDS row between its two pads, the same MAXIT / BCRT instances.  What differs is residency: x[MAXIT], g[MAXIT] per lane and
 // the float64 log-density are loaded ONCE, carried in registers over all the steps (an accepted proposal is taken by select) and stored
 // once at the end; between steps only the optional thinned trajectory goes to HBM.  The arithmetic of a step is mala_chain_step's,
-// operation for operation (same draws, same reductions, no contraction): n_steps launches of mfm_mala_step / mfm_mala_step_keys with
-// the step keys below give the same bits (tests/test_gpu_mala_run.py).  mala_chain_step itself is left alone: it is also the MALA
-// part of the training kernel, whose register allocation is measured.
+// through mcmc.hip.h (the strict form; same draws, same reductions): n_steps launches of mfm_mala_step / mfm_mala_step_keys with
+// the step keys below give the same bits (tests/test_gpu_mala_run.py).
 //
-// Keys.  key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_mala_step uses its key, i.e. chain b draws from
-// split(step key, n_total)[chain_offset + b].  key_mode 1 (chain-major): keys[b] is the chain's own key and step j uses
-// split(keys[b], n_steps)[j] (split_rows on the host, tempered.py:37-39).  Draws are always made in line.
+// Keys (mcmc_run_key).  key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_mala_step uses its key.  key_mode 1
+// (chain-major): keys[b] is the chain's own key and step j uses split(keys[b], n_steps)[j].  Draws are always made in line.
 // (Included by api.hip after mala.hip: MalaArgs, row_value_grad, MALA_DISPATCH.)
 
 struct MalaRunArgs {
@@ -31,10 +29,10 @@ struct MalaRunArgs {
 __device__ __attribute__((noinline)) double run_normal64(Key2 key, uint32_t idx, uint32_t size) { return normal64(key, idx, size); }
 __device__ __attribute__((noinline)) double run_uniform01(Key2 key) { return uniform01(key, 0, 1); }
 __device__ __attribute__((noinline)) double run_exp(double v) { return exp(v); }
+struct RunExp { __device__ __forceinline__ double operator()(double v) const { return run_exp(v); } };
 
 template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r) {
-#pragma clang fp contract(off)      // as mala_chain_step: the steps must round as the single-step launches do
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const MalaArgs& a = r.m;
   const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -56,26 +54,21 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r
   }
   if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
   const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
-  const double s2e = sqrt(2.0 * a.eps);
-  const double inv4e = 0.25 / a.eps;
+  const double s2e = mala_s2e(a.eps);
   int n_acc = 0;
   double acc_sum = 0.0, p_last = 0.0, pw_last = 0.0;
   bool acc_last = false;
 
   for (int s = 0; s < r.n_steps; ++s) {
-    const Key2 kb = r.key_mode ? split_at(kc, (uint32_t)r.n_steps, (uint32_t)s)
-                               : split_at(split_at(a.key, (uint32_t)r.n_steps, (uint32_t)s), a.n_total, a.chain_offset + (uint32_t)b);
-    const Key2 k_int = split_at(kb, 2, 0);                                             // mala.py:93
-    const Key2 k_rmh = split_at(kb, 2, 1);
+    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
+    const Key2 k_int = mcmc_step_key(kb, MCMC_K_INT), k_rmh = mcmc_step_key(kb, MCMC_K_RMH);
     double th1 = 0.0;                       // |x' - x - eps g|^2 = 2 eps |noise|^2
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
       const int j = lane + 64 * it;
       if (j < d) {
-        const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);    // util.py:80-82
-        const double th = s2e * n;
-        th1 += th * th;
-        xn[it] = (float)((double)x[it] + a.eps * (double)g[it] + th);                  // diffusions.py:25-30
+        const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);
+        xn[it] = mala_propose<false>(x[it], g[it], n, a.eps, s2e, th1);
         xs[j] = xn[it];
       }
     }
@@ -86,25 +79,17 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r
     float gn[MAXIT];
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) gn[it] = 0.f;
-    const double lpn = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, gn, gsm);  // diffusions.py:32
+    const double lpn = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, gn, gsm);
     double th2 = 0.0;                       // |x - x' - eps g'|^2
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
       const int j = lane + 64 * it;
-      if (j < d) {
-        const double t = (double)x[it] - (double)xn[it] - a.eps * (double)gn[it];
-        th2 += t * t;
-      }
+      if (j < d) mala_back<false>(x[it], xn[it], gn[it], a.eps, th2);
     }
     th1 = wave_sum(th1); th2 = wave_sum(th2);
-    const double new_E = -lp + inv4e * th1;                                            // mala.py:68-79, proposal.py:157
-    const double prev_E = -lpn + inv4e * th2;                                          // proposal.py:158
-    double delta = prev_E - new_E;                                                     // proposal.py:104
-    if (a.textbook) delta = -delta;
-    if (isnan(delta)) delta = -INFINITY;                                               // proposal.py:105
-    const double p = fmin(run_exp(delta), 1.0);                                            // proposal.py:178
+    const double p = mala_accept_p<false>(lp, lpn, th1, th2, a.eps, a.textbook, RunExp());
     const double u = run_uniform01(k_rmh);
-    const bool acc = u < p;                                                            // proposal.py:179
+    const bool acc = u < p;
     const double lpn0 = __shfl(lpn, 0, 64);     // the value a single-step launch stores (lane 0's) and the next one loads in every lane
 #pragma unroll
     for (int it = 0; it < MAXIT; ++it) {
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r
     acc_sum += p;
     if (s == r.n_steps - 1) {
       p_last = p; acc_last = acc;
-      if (a.prop_weight) pw_last = run_exp(lpn + inv4e * th2);                             // mala.py:104-113 (diagnostic)
+      if (a.prop_weight) pw_last = mala_prop_weight(lpn, th2, a.eps, RunExp());
     }
     if (r.thin > 0 && (s + 1) % r.thin == 0) {
       const size_t snap = (size_t)((s + 1) / r.thin - 1);
@@ -165,8 +150,7 @@ __global__ void mala_run_keys_kernel(int key_mode, Key2 key, const uint32_t* key
                                      uint32_t chain_offset, int B, uint32_t* out) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const Key2 kb = key_mode ? split_at(Key2{keys[2 * b], keys[2 * b + 1]}, n_steps, s)
-                           : split_at(split_at(key, n_steps, s), n_total, chain_offset + (uint32_t)b);
+  const Key2 kb = mcmc_run_key(key_mode, key, key_mode ? Key2{keys[2 * b], keys[2 * b + 1]} : Key2{0, 0}, n_steps, s, n_total, chain_offset + (uint32_t)b);
   out[2 * b] = kb.k0; out[2 * b + 1] = kb.k1;
 }
 

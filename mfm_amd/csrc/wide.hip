@@ -23,7 +23,7 @@
 #include <type_traits>
 #include "dopri5.hip.h"
 #include "mlp.hip.h"
-#include "prng.hip.h"
+#include "mcmc.hip.h"
 
 namespace wide {
 
@@ -1136,8 +1136,8 @@ __global__ __launch_bounds__(256) void flow_accept_kernel(FlowGlue a) {
 }
 
 // ---- MALA step / init for the LGCP target beyond the fused tile kernel's dimension (lgcp.hip handles d <= 1024; the
-//      reference's own pines default is the 40 x 40 grid, multi_modal.py:89).  Same arithmetic as mala_lgcp_kernel, split
-//      around the K^-1 GEMM: propose -> K^-1 (x' - mu) -> energies / accept. ----
+//      reference's own pines default is the 40 x 40 grid, multi_modal.py:89).  Same arithmetic as mala_lgcp_kernel (mcmc.hip.h,
+//      fused form), split around the K^-1 GEMM: propose -> K^-1 (x' - mu) -> energies / accept. ----
 struct LgcpMala {
   TargetDev T; int mode; Key2 key; const uint32_t* keys; uint32_t n_total, chain_offset; int rows, d, dp; double beta, eps; int textbook;
   float* Y; const float* KV; double* th1;
@@ -1146,22 +1146,15 @@ struct LgcpMala {
 __global__ __launch_bounds__(256) void lgcp_propose_kernel(LgcpMala a) {
   const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= a.rows) return;
-  const Key2 kb = a.keys ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b);           // exe_flow_matching.py:303
-  const Key2 k_int = split_at(kb, 2, 0);                                              // mala.py:93
-  const double s2e = sqrt(2.0 * a.eps);
+  const Key2 k_int = mcmc_step_key(mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, b), MCMC_K_INT);
+  const double s2e = mala_s2e(a.eps);
   double th1 = 0.0;
   for (int col = lane; col < a.dp; col += 64) {
     float xn = 0.f;
     if (col < a.d) {
       const size_t o = (size_t)b * a.d + col;
       const float x = a.pos[o];
-      if (a.mode == 1) {
-        const double th = s2e * normal64(k_int, (uint32_t)col, (uint32_t)a.d);        // util.py:80-82
-        th1 += th * th;
-        xn = (float)((double)x + a.eps * (double)a.grad[o] + th);                     // diffusions.py:25-30
-      } else {
-        xn = x;
-      }
+      xn = a.mode == 1 ? mala_propose<true>(x, a.grad[o], normal64(k_int, (uint32_t)col, (uint32_t)a.d), a.eps, s2e, th1) : x;
     }
     a.Y[(size_t)b * a.dp + col] = xn;
   }
@@ -1174,28 +1167,19 @@ __global__ __launch_bounds__(256) void lgcp_accept_kernel(LgcpMala a) {
   double lik = 0.0, quad = 0.0, th2 = 0.0;
   for (int col = lane; col < a.d; col += 64) {
     const float xv = a.Y[(size_t)b * a.dp + col], y = a.KV[(size_t)b * a.dp + col], ex = expf(xv);
-    const float gv = (float)a.beta * (a.T.counts[col] - a.T.poisson_a * ex) - y;
-    lik += (double)xv * (double)a.T.counts[col] - (double)a.T.poisson_a * (double)ex;
-    quad += (double)(xv - a.T.mu) * (double)y;
-    const double t = (double)a.pos[(size_t)b * a.d + col] - (double)xv - a.eps * (double)gv;
-    th2 += t * t;
+    cox_terms(a.T, col, xv, ex, y, lik, quad);
+    mala_back<true>(a.pos[(size_t)b * a.d + col], xv, cox_grad(a.T, a.beta, col, ex, y), a.eps, th2);
   }
   lik = wave_sum(lik); quad = wave_sum(quad); th2 = wave_sum(th2);
-  const double lpn = a.beta * lik - 0.5 * quad + (double)a.T.log_norm;
+  const double lpn = cox_logp(a.T, a.beta, lik, quad);
   bool acc = true;
   if (a.mode == 1) {
-    const double lp = a.logp[b], inv4e = 0.25 / a.eps;
-    const double new_E = -lp + inv4e * a.th1[b], prev_E = -lpn + inv4e * th2;      // mala.py:68-79, proposal.py:157-158
-    double delta = prev_E - new_E;                                                 // proposal.py:104
-    if (a.textbook) delta = -delta;
-    if (isnan(delta)) delta = -INFINITY;                                           // proposal.py:105
-    const double p = fmin(exp(delta), 1.0);                                        // proposal.py:178
-    const Key2 kb = a.keys ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : split_at(a.key, a.n_total, a.chain_offset + (uint32_t)b);
-    acc = uniform01(split_at(kb, 2, 1), 0, 1) < p;                                 // proposal.py:179
+    const double p = mala_accept_p<true>(a.logp[b], lpn, a.th1[b], th2, a.eps, a.textbook);
+    acc = uniform01(mcmc_step_key(mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, b), MCMC_K_RMH), 0, 1) < p;
     if (lane == 0) {
       if (a.acc_prob) a.acc_prob[b] = (float)p;
       if (a.accepted) a.accepted[b] = acc ? 1 : 0;
-      if (a.prop_weight) a.prop_weight[b] = (float)exp(lpn + inv4e * th2);         // mala.py:104-113
+      if (a.prop_weight) a.prop_weight[b] = (float)mala_prop_weight(lpn, th2, a.eps);
     }
   }
   for (int col = lane; col < a.d; col += 64) {
@@ -1203,9 +1187,8 @@ __global__ __launch_bounds__(256) void lgcp_accept_kernel(LgcpMala a) {
     const float xv = a.Y[(size_t)b * a.dp + col];
     if (a.mode == 1 && a.proposed) a.proposed[o] = xv;
     if (acc) {
-      const float gv = (float)a.beta * (a.T.counts[col] - a.T.poisson_a * expf(xv)) - a.KV[(size_t)b * a.dp + col];
       if (a.mode == 1) a.pos[o] = xv;
-      a.grad[o] = gv;
+      a.grad[o] = cox_grad(a.T, a.beta, col, expf(xv), a.KV[(size_t)b * a.dp + col]);
     }
   }
   if (lane == 0 && acc) a.logp[b] = lpn;

@@ -35,7 +35,7 @@ def target_block(dist):
 OPT_KEYS = ("learning_rate", "adam_b1", "adam_b2", "adam_eps", "weight_decay", "update_clip", "learning_iter", "warmup_steps")
 
 
-def make_ctx(dist, args, n_local=None, n_total=None, offset=0, fourier=None, params=None, max_eval=0, family=None, opt=None):
+def make_ctx(dist, args, n_local=None, n_total=None, offset=0, fourier=None, params=None, max_eval=0, family=None, opt=None, n_valid=None):
     """``opt``: optimizer settings (keys OPT_KEYS) that replace the ones taken from ``args``.  They reach the optimizer only: the
     vector field's gradient clip stays ``args.gradient_clip`` (d > 128) whatever ``opt["update_clip"]`` is."""
     from mfm_amd import _lib
@@ -55,7 +55,7 @@ def make_ctx(dist, args, n_local=None, n_total=None, offset=0, fourier=None, par
         ref_std=float(np.sqrt(targets.REF_VARS[getattr(args, "ref_dist", "stdgauss")])),
         ode_method=_lib.ODE_METHODS[getattr(args, "ode_method", "dopri5")] if int(getattr(args, "ode_steps", 0) or 0) > 0 else 0,
         ode_steps=int(getattr(args, "ode_steps", 0) or 0),
-        **({} if family is None else {"kernel_family": family}))
+        **({} if family is None else {"kernel_family": family}), **({} if n_valid is None else {"n_chain_valid": n_valid}))
     kind, blk = target_block(dist)
     ctx.set_target(kind, blk)
     if fourier is not None:
