@@ -268,6 +268,28 @@ int mfm_cis_select(mfm_ctx* ctx, uint32_t key0, uint32_t key1, int n_is, const f
 int mfm_stein_disc(mfm_ctx* ctx, const float* d_x, const float* d_grad, int n, double beta, double h_u_v[2]);
 int mfm_max_mean_disc(mfm_ctx* ctx, const float* d_x, const float* d_y, int m, double* h_out);
 
+/* ---- chain diagnostics (diag.hip): autocorrelation along the time axis of a trajectory and Geyer's initial-positive-sequence
+ *      estimate; mcmc_utils.py:131-165 (autocorrelation) without its FFT.  d_x is float32 [n][n_series], time-major: series s
+ *      is the strided column d_x[t * n_series + s], the layout of mfm_mala_run's d_traj_pos with n_series = n_chain * dim.
+ *      Per series: mean in float64, c_t = x_t - mean, A_k = sum_{t < n-k} c_t c_{t+k}, rho_k = A_k / A_0 for k < n_lags (rho_0 is
+ *      exactly 1; the reference's function returns rho_k / 2, the binding halves); Gamma_m = rho_2m + rho_2m+1,
+ *      tau = -1 + 2 sum of Gamma_m over the leading run of Gamma_m > 0, using only the pairs with 2m + 1 < n_lags (n_lags is the
+ *      max lag), ess = n / tau; var = A_0 / n with A_0 summed in float64.  Any output may be NULL (not all of them); without
+ *      d_rho no [n_lags][n_series] buffer exists anywhere and a series costs only the lags up to its truncation point; d_tau /
+ *      d_ess are bit-identical with and without d_rho.  Lag sums: float32 products summed in float32 inside
+ *      MFM_AUTOCORR_TIME_BLOCK time steps, float64 across (MFM_AUTOCORR_F64=1 at mfm_create: float64 throughout), MFM_AUTOCORR_LAG_BLOCK
+ *      lags per pass over the series.  Deterministic (no atomics); asynchronous on the context's stream; needs no target, Fourier
+ *      block or parameters.
+ *      Edge semantics: a series with A_0 = 0 (constant, or n = 1) yields NaN in rho, tau and ess (the reference divides 0 / 0
+ *      with the warnings silenced), var 0; a non-finite input makes the outputs of ITS series NaN and of no other.
+ *      EINVAL (message names the argument): n < 1, n_series < 1, n_lags outside [1, n], d_x NULL, every output NULL. ---- */
+#define MFM_AUTOCORR_LAG_BLOCK 32
+#define MFM_AUTOCORR_TIME_BLOCK 256
+int mfm_autocorr(mfm_ctx* ctx, const float* d_x, int64_t n, int64_t n_series, int32_t n_lags,
+                 float* d_rho      /* [n_lags][n_series] or NULL */,
+                 float* d_tau, float* d_ess /* [n_series] or NULL; n_lags is then the max lag */,
+                 double* d_mean, double* d_var /* [n_series] or NULL; var = A_0 / n */);
+
 /* ---- draws of the coming iterations, produced ahead of time (noise.hip) -------------------------------------------------
  * Slot j holds the Gaussian / uniform draws of the MALA step keyed h_keys_gn[j] and of the flow-matching batch keyed
  * h_keys_step[j] (uint32 [n_slots][2] each, the keys later passed to mfm_mala_step / mfm_fm_loss_grad).  The request arms

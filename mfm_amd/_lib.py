@@ -39,6 +39,7 @@ class Config(C.Structure):
 
 
 MAX_DEPTH = 3          # include/mfm.h: MFM_MAX_DEPTH
+AUTOCORR_LAG_BLOCK, AUTOCORR_TIME_BLOCK = 32, 256      # include/mfm.h: MFM_AUTOCORR_LAG_BLOCK / _TIME_BLOCK (lags per pass, float32 time block)
 ODE_METHODS = {"dopri5": 0, "rk4": 1, "euler": 2}      # include/mfm.h: MFM_ODE_*
 
 
@@ -89,6 +90,7 @@ _SIGS = {
     "mfm_cis_select": (C.c_int, [_P, _U32, _U32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_stein_disc": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "mfm_max_mean_disc": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_double)]),
+    "mfm_autocorr": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_noise_prefetch": (C.c_int, [_P, C.c_int, C.POINTER(_U32), C.POINTER(_U32)]),
     "mfm_noise_drop": (C.c_int, [_P]),
     "mfm_get_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -442,6 +444,16 @@ class Context:
         out = C.c_double()
         _chk(self.lib.mfm_max_mean_disc(self.h, _ptr(x, F32), _ptr(y, F32), x.shape[0], C.byref(out)))
         return out.value
+
+    def autocorr(self, x, n_lags=None, rho=None, tau=None, ess=None, mean=None, var=None):
+        """``mfm_autocorr`` on the float32 CUDA trajectory ``x [n, ...]`` (time-major: every trailing index is one series).  Outputs
+        (any subset, CUDA tensors): ``rho`` float32 ``[n_lags, n_series]`` (``rho[0] = 1``), ``tau`` / ``ess`` float32 ``[n_series]``
+        (Geyer's initial positive sequence over the first ``n_lags`` lags), ``mean`` / ``var`` float64 ``[n_series]``.  Asynchronous on
+        the context's stream."""
+        n = int(x.shape[0]) if x.ndim else 0
+        n_series = int(x.numel() // n) if n else 0
+        _chk(self.lib.mfm_autocorr(self.h, _ptr(x, F32), n, n_series, int(n if n_lags is None else n_lags), _ptr(rho, F32), _ptr(tau, F32),
+                                   _ptr(ess, F32), _ptr(mean, F64), _ptr(var, F64)))
 
     def beta_update(self, prev_beta, logliks, alpha):
         out = C.c_double()

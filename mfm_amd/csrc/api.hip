@@ -22,6 +22,7 @@
 #include "ode.hip"
 #include "anneal.hip"
 #include "metrics.hip"
+#include "diag.hip"
 #include "cis.hip"
 #include "wide.hip"
 #include "smc.hip"
@@ -99,6 +100,7 @@ struct mfm_ctx {
   Switches sw;                           // the A/B switches as read at mfm_create: installed by every entry point (use_ctx)
   FmMala fuse_mala = {};                 // on != 0 during a mfm_train_iter whose MALA step rides in the training kernel
   int opt_resident_wgs = 0;              // workgroups of reduce_adamw_kernel this device holds at once (occupancy query at create)
+  void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* run_ws = nullptr; size_t run_ws_cap = 0;   // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
 };
 
@@ -392,7 +394,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -1327,6 +1329,31 @@ extern "C" int mfm_max_mean_disc(mfm_ctx* x, const float* d_x, const float* d_y,
   rc = pair_call(x, 1, d_x, nullptr, d_y, nullptr, m, m, 0.f, xy); if (rc) return rc;
   const double m2 = (double)m * (double)m;
   *h_out = (xx[0] - m) / (m2 - m) - 2.0 * xy[0] / m2 + (yy[0] - m) / (m2 - m);      /* mcmc_utils.py:106-110 */
+  return MFM_OK;
+}
+
+// ---- chain diagnostics (diag.hip; mcmc_utils.py:131-165) ----------------------------------------------------------------------
+extern "C" int mfm_autocorr(mfm_ctx* x, const float* d_x, int64_t n, int64_t n_series, int32_t n_lags, float* d_rho, float* d_tau, float* d_ess,
+                            double* d_mean, double* d_var) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (n < 1) return fail(MFM_EINVAL, "n must be at least 1 (got %lld)", (long long)n);
+  if (n_series < 1) return fail(MFM_EINVAL, "n_series must be at least 1 (got %lld)", (long long)n_series);
+  if (n_lags < 1 || n_lags > n) return fail(MFM_EINVAL, "n_lags must be in [1, n = %lld] (got %d)", (long long)n, n_lags);
+  if (!d_rho && !d_tau && !d_ess && !d_mean && !d_var) return fail(MFM_EINVAL, "every output (d_rho, d_tau, d_ess, d_mean, d_var) is null");
+  double* mean_ws = d_mean;
+  if (!mean_ws) {
+    const size_t need = (size_t)n_series * sizeof(double);
+    if (x->ac_ws_cap < need) {
+      if (x->ac_ws) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(x->ac_ws); x->ac_ws = nullptr; x->ac_ws_cap = 0; }
+      HIPCHK(hipMalloc(&x->ac_ws, need));
+      x->ac_ws_cap = need;
+    }
+    mean_ws = (double*)x->ac_ws;
+  }
+  if (launch_autocorr(g_sw.autocorr_f64, d_x, n, n_series, n_lags, d_rho, d_tau, d_ess, mean_ws, d_var, x->stream))
+    return fail(MFM_ETOOLARGE, "n_series = %lld / n_lags = %d exceed the launch grid of the autocorrelation kernel", (long long)n_series, n_lags);
+  LAUNCHCHK();
   return MFM_OK;
 }
 

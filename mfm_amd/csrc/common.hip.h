@@ -38,6 +38,7 @@ struct Switches {
   bool wsk_xcd = false;     // wgrad_sk.hip: consecutive unit ranges on one XCD instead of workgroup w = blockIdx.x (A/B, with MFM_WSK_G)
   bool rccl_comm_stream = false;   // api.hip: the gradient all-reduce of an mfm_adamw_step that has none in flight goes through the communication stream
                                    // (two event hops) instead of in line on the context's own stream (A/B)
+  bool autocorr_f64 = false;   // diag.hip: lag sums in float64 throughout instead of float32 inside a time block (A/B: tools/autocorr_time.py)
   int flow_live = 0;        // chains per workgroup of the shape-specialised flow step: 0 automatic, 16 / 8 / 4 / 2 forced (ode_fast.hip: flow_live_rows)
 };
 static Switches g_sw;
@@ -55,6 +56,7 @@ static void switches_read() {
   s.wide_nocompact = on("MFM_WIDE_NOCOMPACT"); s.wide_no_tbatch = on("MFM_WIDE_NO_TBATCH");
   if (const char* e = getenv("MFM_FLOW_LIVE")) s.flow_live = atoi(e);
   s.tile_exact = on("MFM_TILE_EXACT"); s.wsk_xcd = on("MFM_WSK_XCD"); s.rccl_comm_stream = on("MFM_RCCL_COMM_STREAM");
+  s.autocorr_f64 = on("MFM_AUTOCORR_F64");
   g_sw = s;
 }
 

@@ -433,15 +433,37 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         logger.info(f"Max mean disc of exact samples= {mmd_}")
     else:
         mmd = mmd_ = 0.0                                                                    # :490
+    ess_stats = chain_ess_per_step(eng, dist, args, train_states, key_gen)                  # --ess_steps (build-side addition; {} at 0)
+    if ess_stats:
+        logger.info("ESS per MALA step (min, median, mean over chains and coordinates)= " + ", ".join(f"{v:.4g}" for v in ess_stats.values()))
+        wandb.log(ess_stats)
     res = np.array([logpdf, stein[0], stein[1], mmd, train_time])                           # :561
     res_ = np.array([logpdf_, stein_[0], stein_[1], mmd_, train_time])
     wandb.finish()
     if return_extras:
         return res, res_, dict(metrics=metrics.cpu().numpy(), betas=np.array(betas), lrs=np.array(lrs), states=train_states,
                                engine=eng, state=state, flow_samples=flow_samples, exact_samples=exact_samples, model=model,
-                               final=fin, key_gen=key_gen)
+                               final=fin, key_gen=key_gen, **ess_stats)
     eng.close()
     return res, res_
+
+
+def chain_ess_per_step(eng, dist, args, states, key_gen):
+    """``--ess_steps N``: N MALA steps from the final chains at beta = 1 in one launch (``kernel.run``, ``thin = 1``) and Geyer's effective
+    sample size of every chain and coordinate of that trajectory, over N: ``ess_per_step_min`` / ``_median`` / ``_mean``.  The key is a
+    child of ``key_gen`` that nothing else draws (``split(key_gen, 3)[2]``: the final sampling uses ``split(key_gen)`` and
+    ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are."""
+    n_steps = int(getattr(args, "ess_steps", 0) or 0)
+    if n_steps <= 0 or states.logdensity is None:                  # (training on exact samples keeps no MCMC state)
+        return {}
+    import torch
+    from . import mcmc_utils
+    from .bblackjax.mcmc.mala import mala
+    algo = mala(dist.logprob, args.step_size)
+    _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1)
+    ess, _ = mcmc_utils.effective_sample_size(info.positions[:, :eng.n_valid], ctx=eng.ctx)
+    per_step = (ess.double() / n_steps).reshape(-1)
+    return dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
 
 
 def stein_disc(eng, x, beta=-0.5):

@@ -3,7 +3,7 @@ overrides, ``multi_modal.py:21-101,147-220``), running the MFM loop on MI355X.
 
 Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / ``--force_num_chain`` override the
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
-``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host,
+``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per MALA step after training,
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -163,6 +163,9 @@ def build_parser():
     # the phi-four field's physical dimension: 1 = the chain of the reference's main script, 2 = an L x L lattice in row-major order
     # (dim = L * L must be a perfect square; coefficient a * L, the boundary on both axes)
     parser.add_argument('--phi4_dim_phys', type=int, default=1, choices=[1, 2])
+    # after training: N more MALA steps from the final chains at beta = 1 in one launch, and the effective sample size per step of that
+    # trajectory (mcmc_utils.effective_sample_size) logged as ess_per_step_min / _median / _mean; 0: nothing happens
+    parser.add_argument('--ess_steps', type=int, default=0)
     return parser
 
 
