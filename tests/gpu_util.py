@@ -1,4 +1,6 @@
 """Helpers shared by the -m gpu parity tests: build a device context that mirrors an oracle setup."""
+import os
+
 import numpy as np
 
 from oracle import loop, prng, targets
@@ -88,10 +90,18 @@ def gmm4_setup(B=64, seed=1, hidden=32, F=16, **kw):
     return args, dist, k, model, state
 
 
+PINES_CSV = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "finpines.csv")     # the point pattern of the pine saplings (126 points)
+
+
 def lgcp_setup(n=8, B=32, seed=1, hidden=32, F=16, hutch=True, **kw):
     import os
     d = n * n
-    counts = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mfm_amd", "data", "pines_counts.npz"))[f"counts_{n}"]
+    bundled = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mfm_amd", "data", "pines_counts.npz"))
+    if f"counts_{n}" in bundled.files:
+        counts = bundled[f"counts_{n}"]
+    else:                # a grid without bundled counts: the product's class bins the point pattern (tests/golden/finpines.csv)
+        from mfm_amd.distributions import LogGaussianCoxPines
+        counts = LogGaussianCoxPines(d, file_path=PINES_CSV).counts
     args = loop.default_args(example="pines", dim=d, num_chain=B, hutchs=hutch, step_size=0.01, seed=seed, fourier_dim=F,
                              **hidden_lists(hidden), **kw)
     dist = targets.LogGaussianCoxPines(d, counts)

@@ -11,7 +11,8 @@ def _args(**kw):
     return loop.default_args(**kw)
 
 
-def _run_both(example, d, B, iters, K, hutch=True, width=32, fourier_dim=16, **kw):
+def _run_both(example, d, B, iters, K, hutch=True, width=32, fourier_dim=16, file_path=None, **kw):
+    """``file_path`` (pines only): the point pattern to bin for a grid without bundled counts."""
     from mfm_amd import distributions as D, exe_flow_matching as E
     from oracle import loop, targets
     common = dict(example=example, dim=d, num_chain=B, learning_iter=iters, mcmc_per_flow_steps=float(K), hutchs=hutch,
@@ -22,7 +23,7 @@ def _run_both(example, d, B, iters, K, hutch=True, width=32, fourier_dim=16, **k
         dg, do = D.PhiFour(d), targets.PhiFour(d)
         tg = to = None
     elif example == "pines":
-        dg = D.LogGaussianCoxPines(d)
+        dg = D.LogGaussianCoxPines(d, file_path=file_path)
         do = targets.LogGaussianCoxPines(d, dg.counts)
         tg = to = None
     else:
