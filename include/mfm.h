@@ -163,6 +163,27 @@ int mfm_mala_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const
  * (MFM_EUNSUPPORTED for the Cox process). */
 int mfm_hmc_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, double step_size, int32_t num_steps,
                  float* d_pos, double* d_logp, float* d_grad, float* d_acceptance_rate, uint8_t* d_is_accepted);
+/* the same step for a caller that vmaps over its OWN per-chain keys, as mfm_mala_step_keys: d_keys is uint32[n_chain_local][2],
+ * chain b uses d_keys[b] where mfm_hmc_step uses split(key, n_chain_total)[chain_offset + b]. */
+int mfm_hmc_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double step_size, int32_t num_steps,
+                      float* d_pos, double* d_logp, float* d_grad, float* d_acceptance_rate, uint8_t* d_is_accepted);
+/* n_steps HMC steps (each of num_steps leapfrog steps) in ONE launch, what mfm_mala_run is to mfm_mala_step: the chain stays in
+ * registers between the steps, bit-identical with n_steps single-step calls.
+ * key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_hmc_step uses its key; d_keys is ignored.
+ * key_mode 1 (chain-major): d_keys is uint32[n_chain_local][2]; step j of chain b uses split(d_keys[b], n_steps)[j] as
+ *   mfm_hmc_step_keys uses a chain's key; key0 / key1 are ignored.
+ * State is updated in place.  Optional outputs (NULL to skip): d_n_accepted int32[B], accepted steps; d_acc_sum double[B], sum of
+ * the acceptance probabilities; d_acceptance_rate / d_is_accepted of the LAST step; with thin >= 1 (n_steps % thin == 0, at least
+ * one of the two pointers) the state after every step j with (j + 1) % thin == 0: d_traj_pos float[n_steps / thin][B][dim],
+ * d_traj_logp double[n_steps / thin][B].  thin == 0 keeps no trajectory.  phi-four and mixture targets (MFM_EUNSUPPORTED for the
+ * Cox process, as mfm_hmc_step). */
+int mfm_hmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                double beta, double step_size, int32_t num_steps /* leapfrog steps per HMC step */,
+                int32_t n_steps, int32_t thin,
+                float* d_pos, double* d_logp, float* d_grad,
+                int32_t* d_n_accepted, double* d_acc_sum,
+                float* d_acceptance_rate, uint8_t* d_is_accepted,
+                float* d_traj_pos, double* d_traj_logp);
 /* vmap(dist.loglik) (exe_flow_matching.py:418) */
 int mfm_loglik(mfm_ctx* ctx, const float* d_pos, double* d_out);
 

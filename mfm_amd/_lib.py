@@ -63,6 +63,8 @@ _SIGS = {
     "mfm_mala_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_mala_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_hmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
+    "mfm_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
+    "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_loglik": (C.c_int, [_P, _P, _P]),
     "mfm_smc_delta": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "mfm_smc_weights": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, C.POINTER(C.c_double)]),
@@ -265,6 +267,25 @@ class Context:
         """Build-side mode (``mfm_hmc_step``): one HMC step of every local chain, state updated in place."""
         _chk(self.lib.mfm_hmc_step(self.h, int(key[0]), int(key[1]), float(beta), float(step_size), int(num_steps),
                                    _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(acc, F32), _ptr(is_acc, U8)))
+
+    def hmc_step_keys(self, keys, beta, step_size, num_steps, pos, logp, grad, acc=None, is_acc=None):
+        """``mfm_hmc_step_keys``: ``keys`` is an int32/uint32 device tensor [n_chain_local, 2], one key per chain."""
+        _chk(self.lib.mfm_hmc_step_keys(self.h, _ptr(keys, I32), float(beta), float(step_size), int(num_steps),
+                                        _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(acc, F32), _ptr(is_acc, U8)))
+
+    def hmc_run(self, key, beta, step_size, num_steps, n_steps, pos, logp, grad, thin=0, n_acc=None, acc_sum=None, acc=None,
+                is_acc=None, traj_pos=None, traj_logp=None, key_mode=None):
+        """``mfm_hmc_run``: ``n_steps`` HMC steps of ``num_steps`` leapfrog steps each in one launch, state updated in place.  ``key``
+        as ``mala_run``'s: one key ``(2,)`` (step-major: step j uses ``split(key, n_steps)[j]`` as ``hmc_step`` uses its key) or an
+        int32/uint32 device tensor ``[n_chain_local, 2]`` (chain-major: step j of chain b uses ``split(key[b], n_steps)[j]`` as
+        ``hmc_step_keys`` uses a chain's key).  ``key_mode`` overrides the choice made from the key's shape."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_hmc_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size),
+                                  int(num_steps), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                  _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
+                                  _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
 
     def loglik(self, pos, out):
         _chk(self.lib.mfm_loglik(self.h, _ptr(pos, F32), _ptr(out, F64)))

@@ -4,14 +4,19 @@ BASELINE.json's north star names a "MALA/HMC log-density-and-grad step"; the ref
 ``bblackjax/mcmc`` has no ``hmc.py`` (SURVEY.md note 7), so this module has no counterpart to be a drop-in for.  It follows the kernel of
 blackjax (the package ``bblackjax`` was cut from) with the same conventions as ``mala.py`` here: ``state.position`` is
 ``[n_chain_local, dim]`` (CUDA float32), ``rng_key`` the key BEFORE the per-chain split, ``logdensity_fn`` built from a device target;
-unit mass matrix, velocity Verlet, acceptance ``min(1, exp(H_0 - H_end))`` (``oracle/hmc.py``; device: ``mfm_hmc_step``)."""
+unit mass matrix, velocity Verlet, acceptance ``min(1, exp(H_0 - H_end))`` (``oracle/hmc.py``; device: ``mfm_hmc_step``).  As in
+``mala.py``, a caller that vmaps over its OWN keys passes ``rng_key`` of shape ``[n_chain_local, 2]`` (``mfm_hmc_step_keys``), and the
+kernel carries ``kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin=0)``: ``num_steps`` HMC
+steps in ONE launch (``mfm_hmc_run``) with the chain resident on the device between steps."""
 from typing import Callable, NamedTuple
+
+import numpy as np
 
 from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 from .mala import MALAState as HMCState, _engine, init
 
-__all__ = ["HMCState", "HMCInfo", "init", "build_kernel", "hmc"]
+__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "init", "build_kernel", "hmc"]
 
 
 class HMCInfo(NamedTuple):
@@ -19,17 +24,63 @@ class HMCInfo(NamedTuple):
     is_accepted: object
 
 
+class HMCRunInfo(NamedTuple):
+    """What ``kernel.run`` reports, field for field ``MALARunInfo``: per chain the mean acceptance probability and the number of
+    accepted steps, the LAST step's ``HMCInfo``, and (with ``thin``) the kept states ``positions [num_steps / thin, n_chain, dim]`` /
+    ``logdensities [num_steps / thin, n_chain]`` (``None`` without)."""
+    acceptance_rate: object
+    num_accepted: object
+    last: HMCInfo
+    positions: object
+    logdensities: object
+
+
+def _device_keys(t, rng_key, dev):
+    """Per-chain keys ``[n_chain, 2]`` as the int32 device tensor the library takes (a device tensor passes through)."""
+    return rng_key if t.is_tensor(rng_key) else t.as_tensor(np.ascontiguousarray(rng_key, dtype=np.uint32).view(np.int32), device=dev)
+
+
 def build_kernel():
     def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int):
+        """One key: chain b draws from ``split(rng_key, n_chain_total)[chain_offset + b]``; keys ``[n_chain_local, 2]``: the caller's
+        own vmap, chain b draws from ``rng_key[b]``."""
         dist, beta = resolve_logdensity(logdensity_fn)
         eng = _engine(dist)
         t = eng.torch
         pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()      # states are values
         acc = t.empty(pos.shape[0], device=pos.device, dtype=t.float32)
         isacc = t.empty(pos.shape[0], device=pos.device, dtype=t.uint8)
-        eng.ctx.hmc_step(rng_key, beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
+        if getattr(rng_key, "ndim", 1) == 2:
+            eng.ctx.hmc_step_keys(_device_keys(t, rng_key, pos.device), beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
+        else:
+            eng.ctx.hmc_step(rng_key, beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
         return HMCState(pos, logp, grad), HMCInfo(acc, isacc.bool())
 
+    def run(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int, thin: int = 0):
+        """``num_steps`` calls of ``kernel`` in one: with ONE key step j uses ``split(rng_key, num_steps)[j]`` (the scan of
+        ``inference_loop0``); with keys ``[n_chain_local, 2]`` step j of chain b uses ``split(rng_key[b], num_steps)[j]``.
+        Bit-identical with that loop.  ``thin >= 1`` keeps the state after every ``thin``-th step."""
+        dist, beta = resolve_logdensity(logdensity_fn)
+        eng = _engine(dist)
+        t = eng.torch
+        num_steps, thin = int(num_steps), int(thin)
+        pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()
+        n, dev = pos.shape[0], pos.device
+        n_acc = t.empty(n, device=dev, dtype=t.int32)
+        acc_sum = t.empty(n, device=dev, dtype=t.float64)
+        acc = t.empty(n, device=dev, dtype=t.float32)
+        isacc = t.empty(n, device=dev, dtype=t.uint8)
+        traj_pos = traj_logp = None
+        if thin > 0 and num_steps >= thin and num_steps % thin == 0:       # (anything else: the library names the bad argument)
+            traj_pos = t.empty((num_steps // thin,) + tuple(pos.shape), device=dev, dtype=t.float32)
+            traj_logp = t.empty((num_steps // thin, n), device=dev, dtype=t.float64)
+        if getattr(rng_key, "ndim", 1) == 2:
+            rng_key = _device_keys(t, rng_key, dev)
+        eng.ctx.hmc_run(rng_key, beta, step_size, num_integration_steps, num_steps, pos, logp, grad, thin=thin, n_acc=n_acc,
+                        acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp)
+        return HMCState(pos, logp, grad), HMCRunInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp)
+
+    kernel.run = run
     return kernel
 
 
@@ -46,4 +97,8 @@ class hmc:
         def step_fn(rng_key, state):
             return kernel(rng_key, state, logdensity_fn, step_size, num_integration_steps)
 
+        def run_fn(rng_key, state, num_steps, thin=0):
+            return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin)
+
+        step_fn.run = run_fn
         return SamplingAlgorithm(init_fn, step_fn)

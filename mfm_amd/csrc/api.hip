@@ -15,6 +15,7 @@
 #include "mala_run.hip"
 #include "lgcp.hip"
 #include "hmc.hip"
+#include "hmc_run.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -692,21 +693,65 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
 }
 
 // Build-side mode (hmc.hip; not on the reference's MFM path): one HMC step of every local chain, state updated in place like mfm_mala_step
-extern "C" int mfm_hmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, int num_steps, float* d_pos, double* d_logp,
-                            float* d_grad, float* d_acc, uint8_t* d_isacc) { use_ctx(x);
+static const char* const kHmcNoCox = "the HMC step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)";
+static HmcArgs hmc_args(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
+                        double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
+  HmcArgs a; memset(&a, 0, sizeof a);
+  a.T = x->net.T; a.key = Key2{k0, k1}; a.keys = d_keys; a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local;
+  a.num_steps = num_steps; a.beta = beta; a.eps = step;
+  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.acc_prob = d_acc; a.accepted = d_isacc;
+  return a;
+}
+
+static int hmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
+                           double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
   NEED_TARGET();
   if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
   if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
   if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
-  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "the HMC step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)");
-  HmcArgs a; memset(&a, 0, sizeof a);
-  a.T = x->net.T; a.key = Key2{k0, k1}; a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local;
-  a.num_steps = num_steps; a.beta = beta; a.eps = step;
-  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.acc_prob = d_acc; a.accepted = d_isacc;
+  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  const HmcArgs a = hmc_args(x, k0, k1, d_keys, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_step(a, x->stream)) return too_large(x, "HMC");
   LAUNCHCHK();
   x->ctr[CTR_MALA] += x->cfg.n_chain_local;
+  return MFM_OK;
+}
+
+extern "C" int mfm_hmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, int num_steps, float* d_pos, double* d_logp,
+                            float* d_grad, float* d_acc, uint8_t* d_isacc) { use_ctx(x);
+  return hmc_step_common(x, k0, k1, nullptr, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+}
+extern "C" int mfm_hmc_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos, double* d_logp,
+                                 float* d_grad, float* d_acc, uint8_t* d_isacc) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return hmc_step_common(x, 0, 0, d_keys, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+}
+
+// n_steps HMC steps in one launch (hmc_run.hip): the chain stays in registers between the steps; arguments as mfm_mala_run's
+extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t num_steps,
+                           int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum,
+                           float* d_acc, uint8_t* d_isacc, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
+  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
+  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
+  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
+  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
+  if (thin < 0) return fail(MFM_EINVAL, "thin must not be negative (got %d)", thin);
+  if (thin > 0 && n_steps % thin) return fail(MFM_EINVAL, "thin (%d) must divide n_steps (%d)", thin, n_steps);
+  if (thin > 0 && !d_traj_pos && !d_traj_logp) return fail(MFM_EINVAL, "thin > 0 needs d_traj_pos or d_traj_logp");
+  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  HmcRunArgs r; memset(&r, 0, sizeof r);
+  r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+  r.key_mode = key_mode; r.n_steps = n_steps; r.thin = thin;
+  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum; r.traj_pos = d_traj_pos; r.traj_logp = d_traj_logp;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_hmc_run(r, x->stream)) return too_large(x, "HMC");
+  LAUNCHCHK();
+  // steps only, next to mfm_hmc_step's: CTR_MALA_BYTES is the MALA kernels' traffic and covers no HMC entry point
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;
   return MFM_OK;
 }
 

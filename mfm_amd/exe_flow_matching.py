@@ -435,7 +435,13 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         mmd = mmd_ = 0.0                                                                    # :490
     ess_stats = chain_ess_per_step(eng, dist, args, train_states, key_gen)                  # --ess_steps (build-side addition; {} at 0)
     if ess_stats:
-        logger.info("ESS per MALA step (min, median, mean over chains and coordinates)= " + ", ".join(f"{v:.4g}" for v in ess_stats.values()))
+        use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
+        step_name = f"HMC step ({int(args.hmc_steps)} leapfrog steps)" if use_hmc else "MALA step"
+        logger.info(f"ESS per {step_name} (min, median, mean over chains and coordinates)= "
+                    + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_step_min", "ess_per_step_median", "ess_per_step_mean")))
+        if use_hmc:
+            logger.info("ESS per gradient evaluation of the HMC kernel (min, median, mean)= "
+                        + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_grad_min", "ess_per_grad_median", "ess_per_grad_mean")))
         wandb.log(ess_stats)
     res = np.array([logpdf, stein[0], stein[1], mmd, train_time])                           # :561
     res_ = np.array([logpdf_, stein_[0], stein_[1], mmd_, train_time])
@@ -449,21 +455,33 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
 
 
 def chain_ess_per_step(eng, dist, args, states, key_gen):
-    """``--ess_steps N``: N MALA steps from the final chains at beta = 1 in one launch (``kernel.run``, ``thin = 1``) and Geyer's effective
-    sample size of every chain and coordinate of that trajectory, over N: ``ess_per_step_min`` / ``_median`` / ``_mean``.  The key is a
-    child of ``key_gen`` that nothing else draws (``split(key_gen, 3)[2]``: the final sampling uses ``split(key_gen)`` and
-    ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are."""
+    """``--ess_steps N``: N steps of the kernel the run trained with (``--mcmc_kernel``: MALA steps, or HMC steps of ``--hmc_steps``
+    leapfrog steps) at ``--step_size`` from the final chains at beta = 1 in one launch (``kernel.run``, ``thin = 1``) and Geyer's
+    effective sample size of every chain and coordinate of that trajectory, over N: ``ess_per_step_min`` / ``_median`` / ``_mean``.
+    An HMC step costs ``hmc_steps`` gradient evaluations where a MALA step costs one, so for ``hmc`` the same figures over
+    ``hmc_steps`` come along as ``ess_per_grad_min`` / ``_median`` / ``_mean``: the scale on which the two kernels compare (for MALA
+    it is ``ess_per_step_*`` itself).  The key is a child of ``key_gen`` that nothing else draws (``split(key_gen, 3)[2]``: the final
+    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are."""
     n_steps = int(getattr(args, "ess_steps", 0) or 0)
     if n_steps <= 0 or states.logdensity is None:                  # (training on exact samples keeps no MCMC state)
         return {}
     import torch
     from . import mcmc_utils
-    from .bblackjax.mcmc.mala import mala
-    algo = mala(dist.logprob, args.step_size)
+    use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
+    if use_hmc:
+        from .bblackjax.mcmc.hmc import hmc
+        algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))
+    else:
+        from .bblackjax.mcmc.mala import mala
+        algo = mala(dist.logprob, args.step_size)
     _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1)
     ess, _ = mcmc_utils.effective_sample_size(info.positions[:, :eng.n_valid], ctx=eng.ctx)
     per_step = (ess.double() / n_steps).reshape(-1)
-    return dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
+    out = dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
+    if use_hmc:
+        for name in ("min", "median", "mean"):
+            out["ess_per_grad_" + name] = out["ess_per_step_" + name] / int(args.hmc_steps)
+    return out
 
 
 def stein_disc(eng, x, beta=-0.5):

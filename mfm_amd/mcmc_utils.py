@@ -1,10 +1,10 @@
 """``mcmc_utils.py:11-25``: run an MCMC kernel ``n_iter`` times and keep the trajectory.
 
 The reference scans ``kernel(key, state)`` over ``split(rng, n_iter)`` and returns the stacked ``(states, info)``.  Here a kernel
-that carries ``.run`` (``mala(logdensity_fn, step_size).step``, ``bblackjax/mcmc/mala.py``) does the whole scan in ONE library
-call (``mfm_mala_run`` with ``thin = 1``: the chains stay on the device between steps, same keys, same bits as the loop); any
-other kernel is looped on the host.  (The sample-quality metrics of the reference's module are ``Context.stein_disc`` /
-``Context.max_mean_disc``.)
+that carries ``.run`` (``mala(logdensity_fn, step_size).step``, ``bblackjax/mcmc/mala.py``; ``hmc(logdensity_fn, step_size, L).step``,
+``bblackjax/mcmc/hmc.py``) does the whole scan in ONE library call (``mfm_mala_run`` / ``mfm_hmc_run`` with ``thin = 1``: the
+chains stay on the device between steps, same keys, same bits as the loop); any other kernel is looped on the host.  (The
+sample-quality metrics of the reference's module are ``Context.stein_disc`` / ``Context.max_mean_disc``.)
 
 ``mcmc_utils.py:131-165``: ``autocorrelation`` of a trajectory along one axis, and -- not in the reference, from the same lag sums --
 ``effective_sample_size`` (Geyer's initial positive sequence).  Both run on the device (``mfm_autocorr``, ``csrc/diag.hip``): direct
@@ -38,8 +38,9 @@ def inference_loop0(rng, init_state, kernel, n_iter):
     """``states, info = inference_loop0(rng, init_state, kernel, n_iter)`` with ``kernel(key, state) -> (state, info)``.
 
     ``states`` holds the state AFTER each of the ``n_iter`` steps along a leading axis.  With a kernel that carries ``.run`` the
-    per-step gradients are not kept (``states.logdensity_grad is None``) and ``info`` is the run's ``MALARunInfo`` (acceptance
-    per chain over the run, the last step's ``MALAInfo``) rather than ``n_iter`` stacked infos."""
+    per-step gradients are not kept (``states.logdensity_grad is None``) and ``info`` is the run's ``MALARunInfo`` / ``HMCRunInfo``
+    (acceptance per chain over the run, the last step's ``MALAInfo`` / ``HMCInfo``; any tuple with ``positions`` and
+    ``logdensities`` serves) rather than ``n_iter`` stacked infos."""
     n_iter = int(n_iter)
     run = getattr(kernel, "run", None)
     if run is not None:
