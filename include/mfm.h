@@ -184,6 +184,40 @@ int mfm_hmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const 
                 int32_t* d_n_accepted, double* d_acc_sum,
                 float* d_acceptance_rate, uint8_t* d_is_accepted,
                 float* d_traj_pos, double* d_traj_logp);
+/* STEP-SIZE WARMUP: n_steps steps of the HMC step (mfm_hmc_warmup) or of the MALA step under the textbook rule (mfm_mala_warmup) in
+ * ONE launch, as mfm_hmc_run / mfm_mala_run (chain resident in registers, key_mode 0 / 1 and their key schedules), in which every
+ * chain adapts its OWN step size by Nesterov dual averaging on its acceptance probability (Hoffman & Gelman 2014, algorithm 5).
+ * The constants are fixed: t0 = 10, gamma = 0.05, kappa = 0.75, mu = log(10 * step0).  Per chain, in float64:
+ *     x_0 = log(step0), Hbar_0 = 0, xbar_0 = 0;   for m = 1 .. n_steps:
+ *     1. the step runs with eps_m = exp(x_{m-1}) (eps_1 = step0 itself, not exp(log(step0))) and has the acceptance probability
+ *        p_m: the float64 value before any rounding for an info array, 0 for a NaN energy difference;
+ *     2. Hbar_m = (1 - 1 / (m + t0)) * Hbar_{m-1} + (target_accept - p_m) / (m + t0);
+ *     3. x_m = mu - (sqrt(m) / gamma) * Hbar_m, clamped to [log(step0) - 23, log(step0) + 23] so that eps stays finite and positive;
+ *     4. eta = 1 / (sqrt(m) * sqrt(sqrt(m)))   (m^-kappa from two correctly rounded square roots: a host restatement agrees);
+ *     5. xbar_m = eta * x_m + (1 - eta) * xbar_{m-1}.
+ * Outputs per chain: d_step_avg[b] = exp(xbar_n), the RESULT (required); d_step_last[b] = exp(x_n) (or NULL); d_step_traj
+ * double[n_steps][B], the step size USED at each step (or NULL); d_n_accepted / d_acc_sum as mfm_hmc_run.  Step m of chain b has the
+ * bits of a single-step call (mfm_hmc_step_keys; mfm_mala_step_keys with textbook = 1) with the scalar step size d_step_traj[m][b]
+ * and the same step key.  Chains do not communicate: the caller pools the results, e.g. exp(mean(log d_step_avg)) over the rows
+ * below n_chain_valid (padding rows are stepped like any other).  State is updated in place.
+ * target_accept must lie strictly inside (0, 1).  The Cox process returns MFM_EUNSUPPORTED from both (HMC: as mfm_hmc_step; MALA: its
+ * run is a sequence of tile launches with a by-value step size).  mfm_mala_warmup with textbook = 0 returns MFM_EINVAL: the
+ * as-written rule accepts with min(1, 1 / alpha), its acceptance does not fall as the step grows, and dual averaging has nothing to
+ * steer by. */
+int mfm_hmc_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                   double beta, double step0, int32_t num_steps /* leapfrog steps per HMC step */,
+                   int32_t n_steps, double target_accept,
+                   float* d_pos, double* d_logp, float* d_grad,
+                   double* d_step_avg, double* d_step_last,
+                   int32_t* d_n_accepted, double* d_acc_sum,
+                   double* d_step_traj);
+int mfm_mala_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                    double beta, double step0, int textbook,
+                    int32_t n_steps, double target_accept,
+                    float* d_pos, double* d_logp, float* d_grad,
+                    double* d_step_avg, double* d_step_last,
+                    int32_t* d_n_accepted, double* d_acc_sum,
+                    double* d_step_traj);
 /* vmap(dist.loglik) (exe_flow_matching.py:418) */
 int mfm_loglik(mfm_ctx* ctx, const float* d_pos, double* d_out);
 

@@ -65,6 +65,8 @@ _SIGS = {
     "mfm_hmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
     "mfm_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_hmc_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_mala_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_loglik": (C.c_int, [_P, _P, _P]),
     "mfm_smc_delta": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "mfm_smc_weights": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, C.POINTER(C.c_double)]),
@@ -286,6 +288,41 @@ class Context:
                                   int(num_steps), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                   _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
                                   _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    def _warmup_sizes(self, n_steps, step_avg, step_last, n_acc, acc_sum, step_traj):
+        """The library cannot see a tensor's length: an output shorter than the kernel writes is refused here."""
+        for name, t_ in (("step_avg", step_avg), ("step_last", step_last), ("n_acc", n_acc), ("acc_sum", acc_sum)):
+            if t_ is not None and t_.numel() < self.n_local:
+                raise MfmError(f"{name} must hold n_chain_local = {self.n_local} elements (got {t_.numel()})")
+        if step_traj is not None and step_traj.numel() < max(int(n_steps), 0) * self.n_local:
+            raise MfmError(f"step_traj must hold n_steps * n_chain_local = {int(n_steps) * self.n_local} elements (got {step_traj.numel()})")
+
+    def hmc_warmup(self, key, beta, step0, num_steps, n_steps, target_accept, pos, logp, grad, step_avg, step_last=None, n_acc=None,
+                   acc_sum=None, step_traj=None, key_mode=None):
+        """``mfm_hmc_warmup``: ``n_steps`` HMC steps of ``num_steps`` leapfrog steps each in one launch, every chain adapting its own
+        step size from ``step0`` by dual averaging towards the acceptance probability ``target_accept`` (the recursion:
+        ``include/mfm.h``); state updated in place.  ``key`` / ``key_mode`` as ``hmc_run``'s.  ``step_avg`` (float64 ``[n_chain_local]``,
+        required) takes the averaged step size, the result; ``step_last`` the last iterate; ``step_traj`` (float64
+        ``[n_steps, n_chain_local]``) the step size used at every step."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        self._warmup_sizes(n_steps, step_avg, step_last, n_acc, acc_sum, step_traj)
+        _chk(self.lib.mfm_hmc_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
+                                     int(num_steps), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                     _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
+
+    def mala_warmup(self, key, beta, step0, n_steps, target_accept, pos, logp, grad, step_avg, step_last=None, n_acc=None,
+                    acc_sum=None, step_traj=None, textbook=True, key_mode=None):
+        """``mfm_mala_warmup``: the same for the MALA step under the TEXTBOOK acceptance rule (``textbook=False`` is refused by the
+        library: the as-written rule's acceptance does not fall as the step grows)."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        self._warmup_sizes(n_steps, step_avg, step_last, n_acc, acc_sum, step_traj)
+        _chk(self.lib.mfm_mala_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
+                                      int(textbook), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                      _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
 
     def loglik(self, pos, out):
         _chk(self.lib.mfm_loglik(self.h, _ptr(pos, F32), _ptr(out, F64)))

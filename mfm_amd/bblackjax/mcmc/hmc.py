@@ -7,7 +7,10 @@ blackjax (the package ``bblackjax`` was cut from) with the same conventions as `
 unit mass matrix, velocity Verlet, acceptance ``min(1, exp(H_0 - H_end))`` (``oracle/hmc.py``; device: ``mfm_hmc_step``).  As in
 ``mala.py``, a caller that vmaps over its OWN keys passes ``rng_key`` of shape ``[n_chain_local, 2]`` (``mfm_hmc_step_keys``), and the
 kernel carries ``kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin=0)``: ``num_steps`` HMC
-steps in ONE launch (``mfm_hmc_run``) with the chain resident on the device between steps."""
+steps in ONE launch (``mfm_hmc_run``) with the chain resident on the device between steps, and ``kernel.warmup(rng_key, state,
+logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate=0.8, keep_step_sizes=False)``: ``num_steps`` HMC
+steps in one launch (``mfm_hmc_warmup``) in which every chain adapts its own step size from ``step_size`` by dual averaging towards
+the target acceptance probability (Hoffman & Gelman's constants; the recursion: ``include/mfm.h``)."""
 from typing import Callable, NamedTuple
 
 import numpy as np
@@ -16,7 +19,7 @@ from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 from .mala import MALAState as HMCState, _engine, init
 
-__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "init", "build_kernel", "hmc"]
+__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "HMCWarmupInfo", "init", "build_kernel", "hmc"]
 
 
 class HMCInfo(NamedTuple):
@@ -33,6 +36,38 @@ class HMCRunInfo(NamedTuple):
     last: HMCInfo
     positions: object
     logdensities: object
+
+
+class HMCWarmupInfo(NamedTuple):
+    """What ``kernel.warmup`` reports.  Per chain (``[n_chain_local]``, float64): ``step_size``, the averaged iterate ``exp(xbar_n)``
+    -- the result -- and ``last_step_size`` ``exp(x_n)``; ``pooled_step_size``, ONE float, the geometric mean of ``step_size`` over
+    the chains of all ranks without the padding rows (``mcmc_utils.pooled_step_size``); per chain the mean acceptance probability
+    over the warmup and the number of accepted steps; ``step_sizes [num_steps, n_chain_local]``, the step size USED at every step
+    (``None`` unless asked for)."""
+    step_size: object
+    last_step_size: object
+    pooled_step_size: float
+    acceptance_rate: object
+    num_accepted: object
+    step_sizes: object
+
+
+def _warmup(call, eng, rng_key, state, num_steps, keep_step_sizes):
+    """The buffers of a warmup call, ``call(rng_key, pos, logp, grad, **outputs)``, and its info (shared with ``mala.py``)."""
+    from ...mcmc_utils import pooled_step_size
+    t = eng.torch
+    num_steps = int(num_steps)
+    pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()      # states are values
+    n, dev = pos.shape[0], pos.device
+    step_avg = t.empty(n, device=dev, dtype=t.float64)
+    step_last = t.empty(n, device=dev, dtype=t.float64)
+    n_acc = t.empty(n, device=dev, dtype=t.int32)
+    acc_sum = t.empty(n, device=dev, dtype=t.float64)
+    traj = t.empty((num_steps, n), device=dev, dtype=t.float64) if keep_step_sizes and num_steps >= 1 else None
+    if getattr(rng_key, "ndim", 1) == 2:
+        rng_key = _device_keys(t, rng_key, dev)
+    call(rng_key, pos, logp, grad, step_avg=step_avg, step_last=step_last, n_acc=n_acc, acc_sum=acc_sum, step_traj=traj)
+    return HMCState(pos, logp, grad), HMCWarmupInfo(step_avg, step_last, pooled_step_size(step_avg, eng.n_valid), acc_sum / num_steps, n_acc, traj)
 
 
 def _device_keys(t, rng_key, dev):
@@ -80,7 +115,19 @@ def build_kernel():
                         acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp)
         return HMCState(pos, logp, grad), HMCRunInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp)
 
+    def warmup(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int,
+               target_acceptance_rate: float = 0.8, keep_step_sizes: bool = False):
+        """``num_steps`` HMC steps in one launch, from ``step_size``, every chain adapting its own step size towards
+        ``target_acceptance_rate``; keys as ``run``'s (one key: step-major; ``[n_chain_local, 2]``: chain-major).  Returns the state
+        after the steps and an ``HMCWarmupInfo``; ``info.pooled_step_size`` is the value to sample with."""
+        dist, beta = resolve_logdensity(logdensity_fn)
+        eng = _engine(dist)
+        return _warmup(lambda key, pos, logp, grad, **out: eng.ctx.hmc_warmup(key, beta, step_size, num_integration_steps, int(num_steps),
+                                                                              target_acceptance_rate, pos, logp, grad, **out),
+                       eng, rng_key, state, num_steps, keep_step_sizes)
+
     kernel.run = run
+    kernel.warmup = warmup
     return kernel
 
 
@@ -100,5 +147,9 @@ class hmc:
         def run_fn(rng_key, state, num_steps, thin=0):
             return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin)
 
+        def warmup_fn(rng_key, state, num_steps, target_acceptance_rate=0.8, keep_step_sizes=False):
+            return kernel.warmup(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate, keep_step_sizes)
+
         step_fn.run = run_fn
+        step_fn.warmup = warmup_fn
         return SamplingAlgorithm(init_fn, step_fn)

@@ -14,6 +14,12 @@ Same names and argument meaning as the reference (``MALAState`` / ``MALAInfo`` `
   library call (``mfm_mala_run``), the scan of ``mcmc_utils.py:11-25`` with the chain resident on the device between steps.
 
 The acceptance rule is the reference's AS WRITTEN.  ``build_kernel(textbook=True)`` flips it.
+
+``build_kernel(textbook=True)`` also carries ``kernel.warmup(rng_key, state, logdensity_fn, step_size, num_steps,
+target_acceptance_rate=0.574, keep_step_sizes=False)``: ``num_steps`` steps in one launch (``mfm_mala_warmup``) in which every chain
+adapts its own step size by dual averaging towards the target acceptance probability, as ``hmc.py``'s.  Under the as-written rule
+the call raises with the library's message: that rule accepts with ``min(1, 1 / alpha)``, so its acceptance does not fall as the step
+grows and dual averaging has nothing to steer by.
 """
 from typing import Callable, NamedTuple
 
@@ -133,7 +139,23 @@ def build_kernel(textbook: bool = False):
                          is_acc=isacc, proposed=prop, weight=w, traj_pos=traj_pos, traj_logp=traj_logp, textbook=textbook)
         return MALAState(pos, logp, grad), MALARunInfo(acc_sum / num_steps, n_acc, MALAInfo(acc, isacc.bool(), prop, w), traj_pos, traj_logp)
 
+    def warmup(rng_key, state: MALAState, logdensity_fn: Callable, step_size: float, num_steps: int, target_acceptance_rate: float = 0.574,
+               keep_step_sizes: bool = False):
+        """``num_steps`` MALA steps in one launch, from ``step_size``, every chain adapting its own step size towards
+        ``target_acceptance_rate`` (0.574: the optimal-scaling figure for MALA); keys as ``run``'s.  Returns the state after the steps
+        and an ``HMCWarmupInfo`` (``hmc.py``).  Textbook rule only: ``build_kernel()`` as written raises here (module docstring)."""
+        from .hmc import _warmup
+        dist, beta = resolve_logdensity(logdensity_fn)
+        eng = _engine(dist)
+        if state.position.ndim == 1:
+            raise NotImplementedError("kernel.warmup takes the batched state [n_chain_local, dim]")
+        st, info = _warmup(lambda key, pos, logp, grad, **out: eng.ctx.mala_warmup(key, beta, step_size, int(num_steps), target_acceptance_rate,
+                                                                                   pos, logp, grad, textbook=textbook, **out),
+                           eng, rng_key, state, num_steps, keep_step_sizes)
+        return MALAState(*st), info
+
     kernel.run = run
+    kernel.warmup = warmup
     return kernel
 
 

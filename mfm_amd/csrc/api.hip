@@ -16,6 +16,7 @@
 #include "lgcp.hip"
 #include "hmc.hip"
 #include "hmc_run.hip"
+#include "warmup.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -752,6 +753,63 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
   LAUNCHCHK();
   // steps only, next to mfm_hmc_step's: CTR_MALA_BYTES is the MALA kernels' traffic and covers no HMC entry point
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;
+  return MFM_OK;
+}
+
+// Step-size warmup (warmup.hip): n_steps steps in one launch, every chain adapting its own step size by dual averaging (mfm.h)
+static int warmup_check(mfm_ctx* x, int key_mode, const uint32_t* d_keys, double step0, int32_t n_steps, double target_accept, const float* d_pos,
+                        const double* d_logp, const float* d_grad, const double* d_step_avg) {
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  if (!(step0 > 0)) return fail(MFM_EINVAL, "step_size must be positive");
+  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
+  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
+  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
+  if (!(target_accept > 0 && target_accept < 1)) return fail(MFM_EINVAL, "target_accept must lie strictly inside (0, 1) (got %g)", target_accept);
+  if (!d_step_avg) return fail(MFM_EINVAL, "d_step_avg must not be null");
+  return MFM_OK;
+}
+
+extern "C" int mfm_hmc_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int32_t num_steps,
+                              int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
+                              double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
+  if (const int rc = warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg)) return rc;
+  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
+  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  HmcRunArgs r; memset(&r, 0, sizeof r);
+  r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, num_steps, d_pos, d_logp, d_grad, nullptr, nullptr);
+  r.key_mode = key_mode; r.n_steps = n_steps;
+  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
+  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj};
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_hmc_warmup(r, w, x->stream)) return too_large(x, "HMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+
+extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int textbook,
+                               int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
+                               double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
+  if (const int rc = warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg)) return rc;
+  if (x->net.T.kind == MFM_TARGET_LGCP)
+    return fail(MFM_EUNSUPPORTED, "the step-size warmup serves the phi-four and mixture targets (the Cox process's run is a sequence of tile launches with a by-value step size)");
+  if (!textbook)
+    return fail(MFM_EINVAL, "the step-size warmup needs textbook = 1 (the as-written rule accepts with min(1, 1 / alpha): its acceptance does not fall as the step grows)");
+  const int B = x->cfg.n_chain_local, d = x->cfg.dim;
+  MalaRunArgs r; memset(&r, 0, sizeof r);
+  r.m = mala_args(x, beta);
+  r.m.key = Key2{k0, k1}; r.m.keys = key_mode == 1 ? d_keys : nullptr; r.m.eps = step0; r.m.textbook = textbook;
+  r.m.pos = d_pos; r.m.logp = d_logp; r.m.grad = d_grad;
+  r.key_mode = key_mode; r.n_steps = n_steps;
+  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
+  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj};
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_mala_warmup(r, w, x->stream)) return too_large(x, "MALA");
+  LAUNCHCHK();
+  // state in and out once, as mfm_mala_run; the step sizes that were kept
+  x->ctr[CTR_MALA] += (int64_t)B * n_steps;
+  x->ctr[CTR_MALA_BYTES] += (int64_t)B * 4 * (4 * d + 4) + (int64_t)B * 8 * (1 + (d_step_last ? 1 : 0) + (d_step_traj ? n_steps : 0));
   return MFM_OK;
 }
 

@@ -69,3 +69,22 @@ __device__ __forceinline__ double cox_logp(const TargetDev& T, double beta, doub
 #pragma clang fp contract(off)
   return fma(beta, lik, -0.5 * quad) + (double)T.log_norm;
 }
+// Step-size warmup (warmup.hip; include/mfm.h states the recursion): Nesterov dual averaging of a chain's log step size x towards the
+// acceptance probability `target`, with Hoffman & Gelman's constants t0 = 10, gamma = 0.05, kappa = 0.75.  mu = log(10 step0), x0 = log step0;
+// a chain starts from x = x0, hbar = 0, xbar = 0.  Wave-uniform float64, every operation rounded on its own; m^-kappa is 1 / (sqrt(m) sqrt(sqrt(m))),
+// two correctly rounded square roots, so that a host restatement makes the same numbers.
+struct DualAvg {
+  double mu, x0;            // the shrinkage point, and the centre of the clamp [x0 - 23, x0 + 23] that keeps exp(x) finite and positive
+  double x, hbar, xbar;     // the iterate x_m, the averaged error H_m, the averaged iterate
+};
+// step m = 1, 2, ... has run at exp(s.x) with acceptance probability p: the next iterate and the running average
+__device__ __forceinline__ void dual_avg_update(DualAvg& s, int m, double p, double target) {
+#pragma clang fp contract(off)
+  const double mt = (double)m + 10.0;
+  s.hbar = (1.0 - 1.0 / mt) * s.hbar + (target - p) / mt;
+  const double rm = sqrt((double)m);
+  const double x = s.mu - rm / 0.05 * s.hbar;
+  s.x = fmin(fmax(x, s.x0 - 23.0), s.x0 + 23.0);
+  const double eta = 1.0 / (rm * sqrt(rm));
+  s.xbar = eta * s.x + (1.0 - eta) * s.xbar;
+}

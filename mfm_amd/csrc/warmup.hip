@@ -1,0 +1,203 @@
+// Step-size warmup: n_steps HMC or MALA steps of every chain in ONE launch, in which every chain adapts its OWN step size by dual
+// averaging towards a target acceptance probability (mfm_hmc_warmup / mfm_mala_warmup; the recursion: include/mfm.h, DualAvg in mcmc.hip.h).
+//
+// hmc_warmup_kernel / mala_warmup_kernel are hmc_run_kernel / mala_run_kernel (mapping, residency, key schedule, instances) without the
+// trajectory and the last step's info, and with this wave's step size eps_m in place of the launch's: step m of chain b gives the bits
+// of a single-step launch (mfm_hmc_step_keys; mfm_mala_step_keys with textbook = 1) with the scalar step size eps_m[b] and the same step
+// key (tests/test_gpu_warmup.py).  Every HMC chain makes the same number of leapfrog steps, so different step sizes cost no divergence.
+// A chain adapts from the acceptance probability its step already holds (lane 0's float64 value, before it is rounded for any info):
+// no communication between chains, no host round trip; the caller pools the per-chain results.
+//
+// The adaptation's state is wave-uniform.  It is read back through v_readfirstlane after every update, so it lives in scalar registers
+// over the step and takes no vector register from the trajectory (DESIGN.md section 4.11 has the figures); exp and log are called out of
+// line for the reason mala_run.hip states.
+// (Included by api.hip after hmc_run.hip: HmcRunArgs, HmcResident, HmcCalled, MalaRunArgs, RunExp, run_normal64 / run_uniform01 / run_exp.)
+
+struct WarmupArgs {
+  double target;           // the acceptance probability steered to, inside (0, 1)
+  double* step_avg;        // [B] exp(xbar_n), the result
+  double* step_last;       // [B] exp(x_n) (may be null)
+  double* step_traj;       // [n_steps][B] the step size USED at each step (may be null)
+};
+
+__device__ __attribute__((noinline)) double run_log(double v) { return log(v); }
+
+// lane 0's value, in scalar registers from here on
+__device__ __forceinline__ double wave_first(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ DualAvg warmup_begin(double step0) {
+  const double x0 = wave_first(run_log(step0));
+  return DualAvg{wave_first(run_log(10.0 * step0)), x0, x0, 0.0, 0.0};
+}
+// the run's two tallies, kept wave-uniform (lane 0's values, the ones that are written) so that they too ride in scalar registers over a step
+__device__ __forceinline__ void warmup_tally(int& n_acc, double& acc_sum, bool acc, double p) {
+  n_acc += __builtin_amdgcn_readfirstlane(acc ? 1 : 0);
+  acc_sum = wave_first(acc_sum + wave_first(p));
+}
+// after step m (from 1) with acceptance probability p: the state moves on; returns the next step's size exp(x_m)
+__device__ __forceinline__ double warmup_next(DualAvg& da, int m, double p, double target) {
+  dual_avg_update(da, m, wave_first(p), target);
+  da.x = wave_first(da.x); da.hbar = wave_first(da.hbar); da.xbar = wave_first(da.xbar);
+  return wave_first(run_exp(da.x));
+}
+
+template <int MAXIT, bool BCRT = false>
+__global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs r, WarmupArgs w) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const HmcArgs& a = r.h;
+  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rowlen = d + 2;
+  const int b = blockIdx.x * MALA_WAVES + wave;
+  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
+  float* const xs = smem + wave * rowlen + 1;
+  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
+  const size_t row = (size_t)b * d;
+  const size_t B = (size_t)a.B;
+
+  float x[MAXIT], g[MAXIT];
+  double lp = a.logp[b];
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    x[it] = 0.f; g[it] = 0.f;
+    if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
+  }
+  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
+  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  int n_acc = 0;
+  double acc_sum = 0.0;
+  DualAvg da = warmup_begin(a.eps);
+  double eps = a.eps;                                     // the first step runs at the caller's value itself
+
+  for (int s = 0; s < r.n_steps; ++s) {
+    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
+    if (w.step_traj && lane == 0) w.step_traj[(size_t)s * B + (size_t)b] = eps;
+    HmcResident<MAXIT> st{x, g, lp, false, 0.0};
+    hmc_trajectory<MAXIT, BCRT>(a.T, a.beta, eps, a.num_steps, kb, d, lane, xs, gsm, st, HmcCalled());
+    warmup_tally(n_acc, acc_sum, st.acc, st.pa);
+    eps = warmup_next(da, s + 1, st.pa, w.target);
+    // the next step's first drift overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
+  }
+  const double avg = run_exp(da.xbar);
+  if (lane == 0) {
+    a.logp[b] = lp;
+    w.step_avg[b] = avg;
+    if (w.step_last) w.step_last[b] = eps;
+    if (r.n_acc) r.n_acc[b] = n_acc;
+    if (r.acc_sum) r.acc_sum[b] = acc_sum;
+  }
+}
+
+template <int MAXIT, bool BCRT = false>
+__global__ __launch_bounds__(MALA_WAVES * 64) void mala_warmup_kernel(MalaRunArgs r, WarmupArgs w) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const MalaArgs& a = r.m;
+  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rowlen = d + 2;
+  const int b = blockIdx.x * MALA_WAVES + wave;
+  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
+  float* const xs = smem + wave * rowlen + 1;
+  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
+  const size_t row = (size_t)b * d;
+  const size_t B = (size_t)a.B;
+
+  float x[MAXIT], g[MAXIT], xn[MAXIT];
+  double lp = a.logp[b];
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    x[it] = 0.f; g[it] = 0.f; xn[it] = 0.f;
+    if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
+  }
+  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
+  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  int n_acc = 0;
+  double acc_sum = 0.0;
+  DualAvg da = warmup_begin(a.eps);
+  double eps = a.eps;                                     // the first step runs at the caller's value itself
+
+  for (int s = 0; s < r.n_steps; ++s) {
+    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
+    const Key2 k_int = mcmc_step_key(kb, MCMC_K_INT), k_rmh = mcmc_step_key(kb, MCMC_K_RMH);
+    if (w.step_traj && lane == 0) w.step_traj[(size_t)s * B + (size_t)b] = eps;
+    const double s2e = mala_s2e(eps);
+    double th1 = 0.0;                       // |x' - x - eps g|^2 = 2 eps |noise|^2
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      const int j = lane + 64 * it;
+      if (j < d) {
+        const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);
+        xn[it] = mala_propose<false>(x[it], g[it], n, eps, s2e, th1);
+        xs[j] = xn[it];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the stencil reads its neighbours' proposal elements from this wave's row
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+
+    float gn[MAXIT];
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) gn[it] = 0.f;
+    const double lpn = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, gn, gsm);
+    double th2 = 0.0;                       // |x - x' - eps g'|^2
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      const int j = lane + 64 * it;
+      if (j < d) mala_back<false>(x[it], xn[it], gn[it], eps, th2);
+    }
+    th1 = wave_sum(th1); th2 = wave_sum(th2);
+    const double p = mala_accept_p<false>(lp, lpn, th1, th2, eps, a.textbook, RunExp());
+    const double u = run_uniform01(k_rmh);
+    const bool acc = u < p;
+    const double lpn0 = __shfl(lpn, 0, 64);     // the value a single-step launch stores (lane 0's) and the next one loads in every lane
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      x[it] = acc ? xn[it] : x[it];
+      g[it] = acc ? gn[it] : g[it];
+    }
+    lp = acc ? lpn0 : lp;
+    warmup_tally(n_acc, acc_sum, acc, p);
+    eps = warmup_next(da, s + 1, p, w.target);
+    // the next step overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  }
+
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
+  }
+  const double avg = run_exp(da.xbar);
+  if (lane == 0) {
+    a.logp[b] = lp;
+    w.step_avg[b] = avg;
+    if (w.step_last) w.step_last[b] = eps;
+    if (r.n_acc) r.n_acc[b] = n_acc;
+    if (r.acc_sum) r.acc_sum[b] = acc_sum;
+  }
+}
+
+int launch_hmc_warmup(const HmcRunArgs& r, const WarmupArgs& w, hipStream_t stream) {
+  const HmcArgs& a = r.h;
+  MALA_DISPATCH(hmc_warmup_kernel, r, w);
+  return 0;
+}
+int launch_mala_warmup(const MalaRunArgs& r, const WarmupArgs& w, hipStream_t stream) {
+  const MalaArgs& a = r.m;
+  MALA_DISPATCH(mala_warmup_kernel, r, w);
+  return 0;
+}

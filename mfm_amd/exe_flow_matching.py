@@ -316,6 +316,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     use_real_samples = args.mcmc_per_flow_steps < 0                                        # :328
     if use_real_samples and target_gn is None:
         raise ValueError("mcmc_per_flow_steps < 0 trains on exact samples and needs a target with sample_model (:382-386)")
+    check_adapt_args(args)                                                                  # --adapt_steps (build-side addition)
     learning_iter = args.learning_iter
     iter_per_temp = args.anneal_iter // args.num_anneal_temp                                # :330
     n_iter, n_chain = args.eval_iter, args.num_chain
@@ -358,6 +359,12 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         beta = eng.ctx.beta_update(0.0, eng.all_logliks(pos0), args.alpha)                  # :426
         logger.info(f"Initial beta= {beta}")
     train_states = init_fn(pos0, beta)                                                      # :431
+    adapt_start = time.time()
+    adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
+    if adapt_stats:
+        logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']} (mean acceptance probability over the warmup= {adapt_stats['adapt_acceptance']})")
+        wandb.log(adapt_stats)
+        train_start += time.time() - adapt_start                                            # (train_time stays the training's: the warmup has ended, its result is on the host)
     metrics = torch.zeros(learning_iter, 4, device=eng.dev, dtype=torch.float64)            # loss, acc mean, acc std, target loss
     betas, lrs = [], []
     n_reduced = 0
@@ -449,9 +456,42 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     if return_extras:
         return res, res_, dict(metrics=metrics.cpu().numpy(), betas=np.array(betas), lrs=np.array(lrs), states=train_states,
                                engine=eng, state=state, flow_samples=flow_samples, exact_samples=exact_samples, model=model,
-                               final=fin, key_gen=key_gen, **ess_stats)
+                               final=fin, key_gen=key_gen, **ess_stats, **adapt_stats)
     eng.close()
     return res, res_
+
+
+def check_adapt_args(args):
+    """``--adapt_steps`` needs ``--mcmc_kernel hmc`` and a run that takes MCMC steps: raised before any device work."""
+    n_steps = int(getattr(args, "adapt_steps", 0) or 0)
+    if n_steps < 0:
+        raise ValueError(f"--adapt_steps must not be negative (got {n_steps})")
+    if n_steps > 0 and args.mcmc_per_flow_steps < 0:
+        raise ValueError("--adapt_steps has nothing to adapt with mcmc_per_flow_steps < 0: that run trains on exact samples and takes no MCMC step")
+    if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") != "hmc":
+        raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
+                         "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
+    return n_steps
+
+
+def adapt_step_size(eng, dist, args, pos0, key_gen):
+    """``--adapt_steps N`` (with ``--mcmc_kernel hmc``): N HMC warmup steps of ``--hmc_steps`` leapfrog steps in one launch
+    (``kernel.warmup``, ``mfm_hmc_warmup``) on a COPY of the initial chains ``pos0`` at beta = 1, every chain adapting its own step size
+    from ``--step_size`` by dual averaging towards the acceptance probability ``--adapt_target``.  ``args.step_size`` becomes the pooled
+    value (geometric mean over the chains of all ranks) for the rest of the run, ``--ess_steps`` included; ``pos0``, the chains the
+    training starts from, is not moved.  Returns ``adapted_step_size`` and ``adapt_acceptance``, the mean acceptance probability over
+    the warmup's steps and chains.  The key is a child of ``key_gen`` that nothing else draws (``split(key_gen, 4)[3]``: the final
+    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``, ``--ess_steps`` ``split(key_gen, 3)[2]``)."""
+    n_steps = check_adapt_args(args)
+    if n_steps <= 0:
+        return {}
+    from .bblackjax.mcmc.hmc import hmc
+    from .engine import global_mean_std
+    algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))
+    _, info = algo.step.warmup(jr.split(key_gen, 4)[3], algo.init(pos0), n_steps, float(getattr(args, "adapt_target", 0.8)))
+    args.step_size = info.pooled_step_size
+    acc, _ = global_mean_std(info.acceptance_rate[:eng.n_valid], eng.n_total)
+    return dict(adapted_step_size=info.pooled_step_size, adapt_acceptance=acc.item())
 
 
 def chain_ess_per_step(eng, dist, args, states, key_gen):

@@ -72,6 +72,20 @@ def inference_loop(rng, init_state, kernel, n_iter, param):
     return _stack(states), _stack(infos)
 
 
+def pooled_step_size(step_size, n_valid=None):
+    """The one step size a warmup's per-chain results stand for: ``exp(mean(log step_size[:n_valid]))``, the geometric mean over the
+    chains of ALL ranks (``kernel.warmup`` of ``bblackjax/mcmc/hmc.py`` / ``mala.py``; rows from ``n_valid`` on are padding and are
+    left out).  With more than one rank the sum of the logs and the count go through the default process group in one all-reduce
+    (``engine.allreduce_sum_``, the group of the engine's all-gathers), so every rank holds the same float.  ``step_size``: a
+    float64 tensor ``[n_chain_local]`` on the device or on the CPU."""
+    import torch
+    from .engine import allreduce_sum_
+    x = step_size if n_valid is None else step_size[:int(n_valid)]
+    s = torch.stack([x.double().log().sum(), torch.tensor(float(x.numel()), dtype=torch.float64, device=x.device)])
+    allreduce_sum_(s)
+    return float(torch.exp(s[0] / s[1]).item())
+
+
 _diag = None
 
 

@@ -4,6 +4,7 @@ overrides, ``multi_modal.py:21-101,147-220``), running the MFM loop on MI355X.
 Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / ``--force_num_chain`` override the
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` also per gradient evaluation),
+``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training,
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -166,6 +167,11 @@ def build_parser():
     # after training: N more MALA steps from the final chains at beta = 1 in one launch, and the effective sample size per step of that
     # trajectory (mcmc_utils.effective_sample_size) logged as ess_per_step_min / _median / _mean; 0: nothing happens
     parser.add_argument('--ess_steps', type=int, default=0)
+    # before training (--mcmc_kernel hmc only): N HMC warmup steps on a COPY of the initial chains at beta = 1, every chain adapting its own
+    # step size from --step_size by dual averaging towards the acceptance probability --adapt_target; the pooled result replaces
+    # --step_size for the rest of the run (exe_flow_matching.adapt_step_size); 0: nothing happens.  (--warmup_steps is the learning rate's.)
+    parser.add_argument('--adapt_steps', type=int, default=0)
+    parser.add_argument('--adapt_target', type=float, default=0.8)
     return parser
 
 
