@@ -414,6 +414,13 @@ int mfm_profile_read(mfm_ctx* ctx, double ms_total[8], int64_t launches[8]);   /
 /* ---- test helpers (host only, no GPU needed) ------------------------------------------------------------------- */
 int mfm_pack_index(int k, int n, int KB);       /* float index of W[k][n] inside a packed layer */
 int mfm_pack_index_T(int k, int n, int NB);
+/* Which kernel instance an mfm_fm_loss call of n samples runs on this context (its n & ~15 full 16-row tiles; the rest always go
+ * through one 16-row tile).  Nothing is launched.  0: the 16-row tile every other call uses (or the wide family's row kernels);
+ * otherwise the samples per workgroup of the forward-only kernel (32 or 64: & MFM_EVAL_ROWS_MASK) plus MFM_EVAL_RELU (the ReLU is
+ * a compile-time constant; else the activation is read at run time), MFM_EVAL_CHAIN (the weight stream is chained from layer to
+ * layer) and MFM_EVAL_BCRT (the phi-four boundary is read at run time).  < 0: MFM_E*. */
+enum { MFM_EVAL_ROWS_MASK = 0xff, MFM_EVAL_RELU = 0x100, MFM_EVAL_CHAIN = 0x200, MFM_EVAL_BCRT = 0x400 };
+int mfm_fm_eval_instance(mfm_ctx* ctx, int n);
 int mfm_threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]);
 
 #ifdef __cplusplus

@@ -14,6 +14,7 @@ from .build import LIB
 PHI4, GMM, LGCP = 0, 1, 2
 FLOW_RWMH, FLOW_IMH = 0, 1
 FAMILY_AUTO, FAMILY_TILE, FAMILY_WIDE = 0, 1, 2
+EVAL_ROWS_MASK, EVAL_RELU, EVAL_CHAIN, EVAL_BCRT = 0xff, 0x100, 0x200, 0x400      # mfm_fm_eval_instance
 ACTIVATIONS = {"relu": 0, "tanh": 1, "elu": 2, "gelu": 3, "swish": 4}          # exe_flow_matching.py:39-45
 
 
@@ -104,6 +105,7 @@ _SIGS = {
     "mfm_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "mfm_pack_index": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mfm_pack_index_T": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "mfm_fm_eval_instance": (C.c_int, [_P, C.c_int]),
     "mfm_threefry2x32": (C.c_int, [_U32, _U32, _U32, _U32, C.POINTER(_U32)]),
 }
 EXPORTS = tuple(_SIGS)
@@ -367,6 +369,14 @@ class Context:
         n = samples.shape[0]
         _chk(self.lib.mfm_fm_loss(self.h, int(key[0]), int(key[1]), _ptr(samples, F32), n, n if n_total is None else n_total,
                                   offset, _ptr(loss, F64)))
+
+    def fm_eval_instance(self, n):
+        """The kernel instance an ``fm_loss`` call of ``n`` samples runs (``mfm_fm_eval_instance``; no launch): 0 for the 16-row tile,
+        else rows per workgroup (32 / 64) | ``EVAL_RELU`` | ``EVAL_CHAIN`` | ``EVAL_BCRT``."""
+        rc = self.lib.mfm_fm_eval_instance(self.h, int(n))
+        if rc < 0:
+            _chk(rc)
+        return rc
 
     def adamw_step(self, grads):
         self._p()

@@ -990,6 +990,12 @@ __global__ void pad_tile_kernel(const float* src, int rem, int d, float* dst) {
   }
 }
 
+extern "C" int mfm_fm_eval_instance(mfm_ctx* x, int n) { use_ctx(x);
+  NEED_TARGET();
+  if (n <= 0) return fail(MFM_EINVAL, "sample count must be positive (got %d)", n);
+  return x->wide ? 0 : fm_eval_instance(x->net, n & ~15);
+}
+
 extern "C" int mfm_fm_loss(mfm_ctx* x, uint32_t k0, uint32_t k1, const float* d_samples, int n, int n_total, int offset, double* d_loss) { use_ctx(x);
   NEED_TARGET();
   if (n <= 0) return fail(MFM_EINVAL, "sample count must be positive (got %d)", n);

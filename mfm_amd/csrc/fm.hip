@@ -1019,37 +1019,43 @@ bool fm_mala_fusable(const NetDev& n) {
   return n.act == MFM_ACT_RELU && n.T.kind == MFM_TARGET_PHI4 && tpw <= 2 && n.d <= 128 * tpw;
 }
 
+// The forward-only instance a call of B samples runs: 0 for the 16-chain tile (fm_fwd_bwd_kernel<.., TRAIN = false>), otherwise the
+// samples per workgroup (32 / 64) plus MFM_EVAL_* flags (include/mfm.h).  launch_fm launches what this returns, and
+// mfm_fm_eval_instance reports it, so a test can assert the instance it claims to run.
+int fm_eval_instance(const NetDev& n, int B) {
+  const int r = fm_eval_rows(n, B);
+  if (!r) return 0;
+  if (n.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.T)) return r | MFM_EVAL_BCRT;      // other phi-four boundaries: the run-time activation instances
+  const bool relu = n.act == MFM_ACT_RELU;
+  // the 32-sample relu instance with its five full-width layers chained (0.997 -> 0.985 ms on 409,600 samples; same arithmetic)
+  bool chain = n.d == 2 && n.dp == 16 && !g_sw.eval_no_chain;
+  for (int l : {0, 1, 3, 5, 6}) chain &= n.L[l].Kp % 128 == 0 && n.L[l].Np == 16 * MLP_WAVES_FM;
+  if (r == 32 && relu && chain) return r | MFM_EVAL_RELU | MFM_EVAL_CHAIN;
+  return r | (relu ? MFM_EVAL_RELU : 0);
+}
+
 int launch_fm(const FmArgs& a, bool train, hipStream_t stream) {
-  if (const int r = train ? 0 : fm_eval_rows(a.net, a.B)) {
+  if (const int inst = train ? 0 : fm_eval_instance(a.net, a.B)) {
+    const int r = inst & MFM_EVAL_ROWS_MASK;
     const size_t smr = (size_t)fm_eval_lds_layout(a.net, r).total * sizeof(float);
-#define FM_EVAL_LAUNCH(MT_, ACT_)                                                                                     \
+#define FM_EVAL_LAUNCH(...)                                                                                           \
   do {                                                                                                                \
-    (void)hipFuncSetAttribute((const void*)fm_eval_kernel<MT_, ACT_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr); \
-    hipLaunchKernelGGL((fm_eval_kernel<MT_, ACT_>), dim3((a.B + 16 * MT_ - 1) / (16 * MT_)), dim3(MLP_WAVES_FM * 64), smr, stream, a); \
+    (void)hipFuncSetAttribute((const void*)fm_eval_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr); \
+    hipLaunchKernelGGL((fm_eval_kernel<__VA_ARGS__>), dim3((a.B + r - 1) / r), dim3(MLP_WAVES_FM * 64), smr, stream, a); \
   } while (0)
     FmArgs a2 = a;
     a2.stagger_cycles = g_sw.eval_stagger;       // measured: 1.023 -> 0.994 ms on 409,600 samples (any delay of 20 k .. 70 k cycles)
     const FmArgs& a = a2;
-    const bool relu = a.net.act == MFM_ACT_RELU;
-    if (a.net.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.net.T)) {      // other phi-four boundaries: the run-time activation instances
-      if (r == 32) {
-        (void)hipFuncSetAttribute((const void*)fm_eval_kernel<2, -1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
-        hipLaunchKernelGGL((fm_eval_kernel<2, -1, false, true>), dim3((a.B + 31) / 32), dim3(MLP_WAVES_FM * 64), smr, stream, a);
-      } else {
-        (void)hipFuncSetAttribute((const void*)fm_eval_kernel<4, -1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
-        hipLaunchKernelGGL((fm_eval_kernel<4, -1, false, true>), dim3((a.B + 63) / 64), dim3(MLP_WAVES_FM * 64), smr, stream, a);
-      }
-      return 0;
+    switch (inst) {
+      case 32 | MFM_EVAL_BCRT: FM_EVAL_LAUNCH(2, -1, false, true); break;
+      case 64 | MFM_EVAL_BCRT: FM_EVAL_LAUNCH(4, -1, false, true); break;
+      case 32 | MFM_EVAL_RELU | MFM_EVAL_CHAIN: FM_EVAL_LAUNCH(2, MFM_ACT_RELU, true); break;
+      case 32 | MFM_EVAL_RELU: FM_EVAL_LAUNCH(2, MFM_ACT_RELU); break;
+      case 32: FM_EVAL_LAUNCH(2, -1); break;
+      case 64 | MFM_EVAL_RELU: FM_EVAL_LAUNCH(4, MFM_ACT_RELU); break;
+      case 64: FM_EVAL_LAUNCH(4, -1); break;
+      default: return -3;
     }
-    // the 32-sample relu instance with its five full-width layers chained (0.997 -> 0.985 ms on 409,600 samples; same arithmetic)
-    bool chain = a.net.d == 2 && a.net.dp == 16 && !g_sw.eval_no_chain;
-    for (int l : {0, 1, 3, 5, 6}) chain &= a.net.L[l].Kp % 128 == 0 && a.net.L[l].Np == 16 * MLP_WAVES_FM;
-    if (r == 32 && relu && chain) {
-      (void)hipFuncSetAttribute((const void*)fm_eval_kernel<2, MFM_ACT_RELU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smr);
-      hipLaunchKernelGGL((fm_eval_kernel<2, MFM_ACT_RELU, true>), dim3((a.B + 31) / 32), dim3(MLP_WAVES_FM * 64), smr, stream, a);
-    } else
-    if (r == 32) { if (relu) FM_EVAL_LAUNCH(2, MFM_ACT_RELU); else FM_EVAL_LAUNCH(2, -1); }
-    else { if (relu) FM_EVAL_LAUNCH(4, MFM_ACT_RELU); else FM_EVAL_LAUNCH(4, -1); }
 #undef FM_EVAL_LAUNCH
     return 0;
   }

@@ -100,7 +100,7 @@ def test_gmm16_mala_fm_and_exact_trace_flow_step_match_oracle():
     ctx.close(); ctx2.close()
 
 
-def test_gmm16_full_size_iteration_and_eval_batch():
+def test_gmm16_full_size_iteration_and_eval_batch(monkeypatch):
     """configs[1] at its full size: 4096 chains and the 409,600 exact samples of eval_step (:370-374, eval_iter = 100).
     (a) the eval loss on the 409,600 samples the target's own sampler draws is the sum of its chunks and, on one chunk, the
     oracle's; (b) a MALA step + loss/gradient at 4096 chains agree with the oracle on the chains it can afford (draws are
@@ -128,21 +128,27 @@ def test_gmm16_full_size_iteration_and_eval_batch():
     ctx.fm_loss(key_loss, xs[:1024], part, n_total=n_eval, offset=0)
     lo, _ = fm.loss_and_grad(model, params, key_loss, real[:1024].astype(np.float64), args.sigma, need_grad=False, n_total=n_eval, start=0)
     assert abs(part.item() - lo) < 2e-5 * abs(lo)
-    # large sample sets of the mixtures run the 64-samples-per-workgroup forward kernel (fm_eval64_kernel); MFM_EVAL16 routes
-    # them through the 16-row kernel every other call uses: the same per-sample arithmetic, another grouping of the partial sums.
-    # Also a sample count that is not a multiple of 64 (the last workgroup is partly empty) and the oracle on that set.
-    import os
+    # large sample sets of the mixtures run the forward-only kernel (fm_eval_kernel: 32 samples per workgroup, chained weight stream);
+    # MFM_EVAL16 routes them through the 16-row kernel every other call uses: the same per-sample arithmetic, another grouping of
+    # the partial sums.  The switches are read once per mfm_create, so the second arm is its OWN context created under the switch,
+    # and both arms are asserted through mfm_fm_eval_instance.  Also a sample count that is not a multiple of 32 (the last
+    # workgroup is partly empty) and the oracle on that set.
+    from mfm_amd import _lib
     n_odd = 16384 + 48
+    assert ctx.fm_eval_instance(n_odd) == ctx.fm_eval_instance(n_eval) == 32 | _lib.EVAL_RELU | _lib.EVAL_CHAIN
     ctx.fm_loss(key_loss, xs[:n_odd], part, n_total=n_eval, offset=0); l64 = part.item()
-    os.environ["MFM_EVAL16"] = "1"
-    try:
-        ctx.fm_loss(key_loss, xs[:n_odd], part, n_total=n_eval, offset=0); l16 = part.item()
-        ctx.fm_loss(key_loss, xs, part, n_total=n_eval, offset=0); f16 = part.item()
-    finally:
-        del os.environ["MFM_EVAL16"]
-    # (each lane first sums its own squared residuals in float32 -- 4 with 16 rows per workgroup, 16 with 64 -- before the float64
-    # reduction: measured 1.4e-9 relative)
+    monkeypatch.setenv("MFM_EVAL16", "1")
+    ctx16 = gu.make_ctx(dist, args, fourier=model.f, params=params, max_eval=n_eval)
+    monkeypatch.delenv("MFM_EVAL16")
+    assert ctx16.fm_eval_instance(n_odd) == ctx16.fm_eval_instance(n_eval) == 0
+    assert ctx.fm_eval_instance(n_odd) != 0                    # a later context does not change what an earlier one launches
+    ctx16.fm_loss(key_loss, xs[:n_odd], part, n_total=n_eval, offset=0); l16 = part.item()
+    ctx16.fm_loss(key_loss, xs, part, n_total=n_eval, offset=0); f16 = part.item()
+    ctx16.close()
+    # (each lane first sums its own squared residuals in float32 before the float64 reduction, and the first x layer runs on the
+    # vector ALU in the forward-only kernel: measured 1.4e-9 relative)
     assert abs(l64 - l16) < 1e-7 * abs(l16) and abs(full.item() - f16) < 1e-7 * abs(f16), (l64, l16, full.item(), f16)
+    assert l64 != l16, (l64, l16)                              # two kernels, not one kernel twice
     lo, _ = fm.loss_and_grad(model, params, key_loss, real[:n_odd].astype(np.float64), args.sigma, need_grad=False, n_total=n_eval, start=0)
     assert abs(l64 - lo) < 2e-5 * abs(lo)
     # (b) one iteration's kernels at 4096 chains vs the oracle on chains [0, 64)

@@ -82,6 +82,8 @@ def test_eval_kernel_loss(monkeypatch, rows, bc):
     args, dist, dist0, model, model0 = _setup(d, 16, bc, 32, 16)
     params = gu.rand_params(model, seed=3)
     ctx = _ctx(dist, args, fourier=model.f, params=params, max_eval=n)
+    from mfm_amd import _lib
+    assert ctx.fm_eval_instance(n) == int(rows) | _lib.EVAL_BCRT            # fm_eval_kernel<2 | 4, -1, false, BCRT>
     x = np.random.default_rng(5).uniform(-1, 1, (n, d)).astype(np.float32)
     key = prng.PRNGKey(12)
     loss_o, _ = fm.loss_and_grad(model, params, key, x.astype(np.float64), args.sigma)
