@@ -422,6 +422,16 @@ int mfm_pack_index_T(int k, int n, int NB);
 enum { MFM_EVAL_ROWS_MASK = 0xff, MFM_EVAL_RELU = 0x100, MFM_EVAL_CHAIN = 0x200, MFM_EVAL_BCRT = 0x400 };
 int mfm_fm_eval_instance(mfm_ctx* ctx, int n);
 int mfm_threefry2x32(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t out[2]);
+/* The stream-K weight-gradient plan (wgrad_sk.hip) for n_jobs 64 x 64 blocks, nbb 16-chain tiles and at most `cap` resident workgroups;
+ * needs no context and no GPU.  U = n_jobs * nbb units over G workgroups: the first r take q + 1 consecutive units, the others q.
+ * g_override = 0: the default G; otherwise the G that MFM_WSK_G would request (ignored, as there, outside [n_jobs, min(U, cap)]).
+ * h_out = {G, q, r, n_slices}, n_slices the sum over the blocks of their contributor counts; h_wg (may be NULL) is int32 [G][4] =
+ * {j0, bb0, cnt, n0}: workgroup w holds cnt units from tile bb0 of block j0, the first n0 of them in block j0, the rest in j0 + 1. */
+int mfm_wsk_plan(int n_jobs, int nbb, int cap, int g_override, int32_t h_out[4], int32_t* h_wg);
+/* Which weight-gradient kernel mfm_fm_loss_grad / mfm_train_iter launch on this context; nothing is launched.
+ * h_out = {kind, n_jobs, nbb, G, q, r}.  kind 0: the slab kernels (G = n_jobs * split workgroups, slices of q or q + 1 tiles, r = nbb %
+ * split); 1: stream-K (G, q, r as mfm_wsk_plan); 2: the wide family (G workgroups, q of them the workgroup-per-job tail, r = 0). */
+int mfm_wgrad_info(mfm_ctx* ctx, int32_t h_out[6]);
 
 #ifdef __cplusplus
 }

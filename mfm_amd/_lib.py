@@ -107,6 +107,8 @@ _SIGS = {
     "mfm_pack_index_T": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "mfm_fm_eval_instance": (C.c_int, [_P, C.c_int]),
     "mfm_threefry2x32": (C.c_int, [_U32, _U32, _U32, _U32, C.POINTER(_U32)]),
+    "mfm_wsk_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mfm_wgrad_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -153,6 +155,23 @@ F32, F64, U8, I32 = "float32", "float64", "uint8", "int32"
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def wsk_plan(n_jobs, nbb, cap, g_override=0, ranges=True):
+    """``mfm_wsk_plan`` (host only): the stream-K weight-gradient plan as ``dict(G, q, r, n_slices)``, with ``ranges`` also ``wg``,
+    an int32 array ``[G, 4]`` of ``(j0, bb0, cnt, n0)`` per workgroup."""
+    lib = load()
+    out = (C.c_int32 * 4)()
+    _chk(lib.mfm_wsk_plan(int(n_jobs), int(nbb), int(cap), int(g_override), out, None))
+    plan = dict(G=out[0], q=out[1], r=out[2], n_slices=out[3])
+    if ranges:
+        wg = np.empty((plan["G"], 4), dtype=np.int32)
+        _chk(lib.mfm_wsk_plan(int(n_jobs), int(nbb), int(cap), int(g_override), out, wg.ctypes.data_as(C.POINTER(C.c_int32))))
+        plan["wg"] = wg
+    return plan
+
+
+WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2      # mfm_wgrad_info: kind
 
 
 class Context:
@@ -377,6 +396,13 @@ class Context:
         if rc < 0:
             _chk(rc)
         return rc
+
+    def wgrad_info(self):
+        """The weight-gradient kernel this context launches (``mfm_wgrad_info``; no launch): ``dict(kind, n_jobs, nbb, G, q, r)``,
+        ``kind`` one of ``WGRAD_SLABS`` / ``WGRAD_STREAM_K`` / ``WGRAD_WIDE``."""
+        out = (C.c_int32 * 6)()
+        _chk(self.lib.mfm_wgrad_info(self.h, out))
+        return dict(zip(("kind", "n_jobs", "nbb", "G", "q", "r"), [int(v) for v in out]))
 
     def adamw_step(self, grads):
         self._p()

@@ -79,6 +79,7 @@ struct mfm_ctx {
   float* wsk_partials = nullptr; int* wsk_tickets = nullptr;      // stream-K weight gradients (wgrad_sk.hip): partial blocks, arrival counters [2][n_jobs]
   WskConst* wsk_const = nullptr; WskWg* wsk_wg = nullptr;           // its tables, in device memory
   int wsk_G = 0, wsk_par = 0;                                       // its grid (0: the slab kernels serve this context), parity of the arrival counters
+  int wsk_q = 0, wsk_r = 0;                                         // its units per workgroup (wsk_plan)
   int sus_par = 0;                                                  // parity of the training kernel's "suspicious values" word (flag[5 + parity])
   float* eval_pad = nullptr;   // [16][dim]: the last, partial 16-row tile of a mfm_fm_loss call whose n is not a multiple of 16
   WgradJob* jobs; int n_jobs, split;
@@ -326,7 +327,8 @@ static int create_impl(const mfm_config& c, mfm_ctx* x) {
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wgrad_sk_kernel, 256, 0));
     WskConst h; memset(&h, 0, sizeof h);
     int G = 0;
-    if (per_cu * cus >= x->n_jobs) wsk_plan(x->n_jobs, nbb, per_cu * cus, G, h.upw_q, h.upw_r);
+    const char* g_env = getenv("MFM_WSK_G");
+    if (per_cu * cus >= x->n_jobs) wsk_plan(x->n_jobs, nbb, per_cu * cus, g_env ? atoi(g_env) : 0, G, h.upw_q, h.upw_r);
     if (G >= x->n_jobs && h.upw_q >= 1) {
       h.net = n; h.nbb = nbb; h.n_jobs = x->n_jobs; h.G = G;
       ALLOC(x->wsk_partials, (size_t)2 * G * WSK_PSZ); ALLOC(x->wsk_tickets, 2 * x->n_jobs); ALLOC(x->wsk_const, 1);
@@ -344,22 +346,14 @@ static int create_impl(const mfm_config& c, mfm_ctx* x) {
           o.a_row[wv] = wgrad_a_tile(n, x->ws, J.layer, J.kt0 + wv < KT ? J.kt0 + wv : J.kt0);
           o.z_row[wv] = wgrad_z_tile(x->ws, J.layer, J.nt0 + wv < NT ? J.nt0 + wv : J.nt0);
         }
-        h.n_slices += wsk_wg_of(h.upw_q, h.upw_r, (j + 1) * nbb - 1) - wsk_wg_of(h.upw_q, h.upw_r, j * nbb) + 1;
       }
+      h.n_slices = wsk_n_slices(x->n_jobs, nbb, h.upw_q, h.upw_r);
       HIPCHK(hipMemcpy(x->wsk_const, &h, sizeof h, hipMemcpyHostToDevice));
       std::vector<WskWg> wg(G);
-      for (int wq = 0; wq < G; ++wq) {
-        WskWg& d = wg[wq];
-        const int u0 = wsk_start(h.upw_q, h.upw_r, wq);
-        d.cnt = h.upw_q + (wq < h.upw_r ? 1 : 0); d.j0 = u0 / nbb; d.bb0 = u0 - d.j0 * nbb; d.n0 = d.cnt < nbb - d.bb0 ? d.cnt : nbb - d.bb0;
-        for (int sg = 0; sg < 2; ++sg) {
-          const WskJob& J = h.jobs[d.j0 + sg < x->n_jobs ? d.j0 + sg : d.j0];
-          for (int wv = 0; wv < 4; ++wv) { d.a_row[sg][wv] = J.a_row[wv]; d.z_row[sg][wv] = J.z_row[wv]; }
-        }
-      }
+      wsk_ranges(x->n_jobs, nbb, G, h.upw_q, h.upw_r, h.jobs, wg.data());
       ALLOC(x->wsk_wg, G);
       HIPCHK(hipMemcpy(x->wsk_wg, wg.data(), sizeof(WskWg) * G, hipMemcpyHostToDevice));
-      x->wsk_G = G;
+      x->wsk_G = G; x->wsk_q = h.upw_q; x->wsk_r = h.upw_r;
     }
   }
   ALLOC(x->jobs, x->n_jobs); ALLOC(x->opt, 1); ALLOC(x->opt_alt, 1); ALLOC(x->flag, 8); ALLOC(x->beta_out, 4);
@@ -916,7 +910,7 @@ static bool opt_fusable(mfm_ctx* x) {
   // margin for other queues' kernels and for a CU mask narrower than the device (headline: 837 of 2048 on a full MI355X; a
   // 32-CU partition holds 256 and falls back to reduce_slabs + adamw)
   const int grid = (x->net.n_params + 255) / 256;
-  if (x->wsk_G) return !g_sw.no_fused_opt && !x->wide && !x->comm && x->cfg.n_chain_total == x->cfg.n_chain_local;      // (wgrad_sk.hip: no workgroup waits on another)
+  if (x->wsk_G) return !g_sw.no_fused_opt && !x->wide && !x->comm && x->cfg.n_chain_total == x->cfg.n_chain_local;      // (wgrad_sk.hip: its workgroups DO wait for one another; the residency guard is at mfm_create and needs no bound on the parameter count)
   return !g_sw.no_fused_opt && !x->wide && !x->comm && x->cfg.n_chain_total == x->cfg.n_chain_local && 2 * grid <= x->opt_resident_wgs;
 }
 
@@ -928,7 +922,7 @@ static int fm_loss_grad_impl(mfm_ctx* x, uint32_t k0, uint32_t k1, const float* 
   if (rc || x->wide) return rc;
   const int sus_par = x->sus_par; x->sus_par ^= 1;      // (the training kernel just wrote flag[5 + sus_par] and cleared the other word)
   if (x->wsk_G) {
-    // stream-K weight gradients; the last arriver of every block totals it and, with the optimizer, updates it (wgrad_sk.hip)
+    // stream-K weight gradients; every contributor of a block totals its own slice of it and, with the optimizer, updates it (wgrad_sk.hip)
     WskArgs k; memset(&k, 0, sizeof k);
     k.C = x->wsk_const; k.wg = x->wsk_wg; k.acts = x->acts; k.dzs = x->dzs; k.nbb = x->cfg.n_chain_local / 16; k.G = x->wsk_G;
     k.xcd_remap = g_sw.wsk_xcd ? 1 : 0;
@@ -990,6 +984,34 @@ __global__ void pad_tile_kernel(const float* src, int rem, int d, float* dst) {
   }
 }
 
+extern "C" int mfm_wsk_plan(int n_jobs, int nbb, int cap, int g_override, int32_t h_out[4], int32_t* h_wg) {
+  if (!h_out) return fail(MFM_EINVAL, "mfm_wsk_plan: h_out is null");
+  if (n_jobs < 1 || nbb < 1 || cap < n_jobs) return fail(MFM_EINVAL, "mfm_wsk_plan: n_jobs=%d nbb=%d cap=%d (all positive, cap >= n_jobs: one workgroup per block must be resident)", n_jobs, nbb, cap);
+  if ((long long)n_jobs * nbb > 0x7fffffffLL) return fail(MFM_ETOOLARGE, "mfm_wsk_plan: %d x %d units", n_jobs, nbb);
+  int G = 0, q = 0, r = 0;
+  wsk_plan(n_jobs, nbb, cap, g_override, G, q, r);
+  h_out[0] = G; h_out[1] = q; h_out[2] = r; h_out[3] = wsk_n_slices(n_jobs, nbb, q, r);
+  if (h_wg) {
+    std::vector<WskWg> wg(G);
+    wsk_ranges(n_jobs, nbb, G, q, r, nullptr, wg.data());
+    for (int w = 0; w < G; ++w) { h_wg[4 * w] = wg[w].j0; h_wg[4 * w + 1] = wg[w].bb0; h_wg[4 * w + 2] = wg[w].cnt; h_wg[4 * w + 3] = wg[w].n0; }
+  }
+  return MFM_OK;
+}
+extern "C" int mfm_wgrad_info(mfm_ctx* x, int32_t h_out[6]) { use_ctx(x);
+  if (!x || !h_out) return fail(MFM_EINVAL, "mfm_wgrad_info: null argument");
+  const int nbb = x->cfg.n_chain_local / 16;
+  if (x->wide) {
+    int n_full = 0, n_tail = 0;
+    wide::wgrad_grid(x->wide, x->cfg.n_chain_local, n_full, n_tail);
+    h_out[0] = 2; h_out[1] = x->wide->n_jobs; h_out[2] = nbb; h_out[3] = n_full / 4 + n_tail; h_out[4] = n_tail; h_out[5] = 0;
+  } else if (x->wsk_G) {
+    h_out[0] = 1; h_out[1] = x->n_jobs; h_out[2] = nbb; h_out[3] = x->wsk_G; h_out[4] = x->wsk_q; h_out[5] = x->wsk_r;
+  } else {
+    h_out[0] = 0; h_out[1] = x->n_jobs; h_out[2] = nbb; h_out[3] = x->n_jobs * x->split; h_out[4] = nbb / x->split; h_out[5] = nbb % x->split;
+  }
+  return MFM_OK;
+}
 extern "C" int mfm_fm_eval_instance(mfm_ctx* x, int n) { use_ctx(x);
   NEED_TARGET();
   if (n <= 0) return fail(MFM_EINVAL, "sample count must be positive (got %d)", n);

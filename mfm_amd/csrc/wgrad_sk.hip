@@ -8,8 +8,9 @@
 // packed activations were written by the training kernel a launch ago), and a third launch then sums the eight slabs and runs AdamW.
 // Here:
 //  * the work is cut into UNITS (block, chain tile) -- 52 x 256 = 13,312 at the headline shape -- and dealt out evenly and
-//    contiguously: 512 workgroups x 26 units, two workgroups per CU on every CU.  A workgroup's range crosses at most one block
-//    boundary (its range is never longer than a block's chain axis), so it produces at most two partial blocks;
+//    contiguously (wsk_plan): by default 52 blocks x 8 chain slices = 416 workgroups x 32 units there, every workgroup inside one
+//    block (512 workgroups x 26 units, two per CU on every CU, measured slower: see wsk_plan).  In general a workgroup's range
+//    crosses at most one block boundary (it is never longer than a block's chain axis), so it produces at most two partial blocks;
 //  * operands travel global -> LDS by LDS-DMA (global_load_lds_dwordx4: one packed 16 x 16 tile = 1 KB = one wave instruction,
 //    no staging registers, no ds_write pass) into a ring of WSK_NS stages of WSK_TB chain tiles, WSK_NS - 1 stages in flight
 //    behind a COUNTED vmcnt and a raw s_barrier (a __syncthreads() would drain the ring: cdna_hip_programming.md section 5); the
@@ -416,13 +417,32 @@ __global__ __launch_bounds__(256, 2) void wgrad_sk_kernel(const WskWg* wg_tab, c
 //   the same, consecutive ranges on one XCD                                                   39.7 us
 //   416 workgroups = 52 blocks x 8 slices of 32 tiles, slice = XCD (~49 MB; 160 CUs carry two workgroups)   37.0 us
 // (the slab kernels it replaces: 28.5 + 12.5 us).  Eight slices also make the sums bit-identical with those kernels' eight slabs.
-static void wsk_plan(int n_jobs, int nbb, int cap, int& G, int& q, int& r) {
+static void wsk_plan(int n_jobs, int nbb, int cap, int g_req, int& G, int& q, int& r) {
   const int U = n_jobs * nbb;
   int S = nbb < 8 ? nbb : 8;
   while (S > 1 && n_jobs * S > cap) --S;         // (every workgroup must be resident: api.hip)
   G = n_jobs * S;
-  if (const char* e = getenv("MFM_WSK_G")) { const int v = atoi(e); if (v >= n_jobs && v <= U && v <= cap) G = v; }      // development: A/B of the decomposition
+  if (g_req >= n_jobs && g_req <= U && g_req <= cap) G = g_req;      // (MFM_WSK_G; development: A/B of the decomposition)
   q = U / G; r = U - q * G;                      // a range is never longer than one block's chain axis: at most two partial blocks per workgroup
+}
+// sum over the blocks of their contributor counts, as the kernel derives them (nc in its combine loop)
+static int wsk_n_slices(int n_jobs, int nbb, int q, int r) {
+  int n = 0;
+  for (int j = 0; j < n_jobs; ++j) n += wsk_wg_of(q, r, (j + 1) * nbb - 1) - wsk_wg_of(q, r, j * nbb) + 1;
+  return n;
+}
+// the unit range of every workgroup; with `jobs` also the tile rows its waves fetch in either segment
+static void wsk_ranges(int n_jobs, int nbb, int G, int q, int r, const WskJob* jobs, WskWg* wg) {
+  for (int w = 0; w < G; ++w) {
+    WskWg& d = wg[w];
+    const int u0 = wsk_start(q, r, w);
+    d.cnt = q + (w < r ? 1 : 0); d.j0 = u0 / nbb; d.bb0 = u0 - d.j0 * nbb; d.n0 = d.cnt < nbb - d.bb0 ? d.cnt : nbb - d.bb0;
+    if (!jobs) continue;
+    for (int sg = 0; sg < 2; ++sg) {
+      const WskJob& J = jobs[d.j0 + sg < n_jobs ? d.j0 + sg : d.j0];
+      for (int wv = 0; wv < 4; ++wv) { d.a_row[sg][wv] = J.a_row[wv]; d.z_row[sg][wv] = J.z_row[wv]; }
+    }
+  }
 }
 int launch_wgrad_sk(const WskArgs& a, int G, hipStream_t stream) {
   hipLaunchKernelGGL(wgrad_sk_kernel, dim3(G), dim3(256), 0, stream, a.wg, a.acts, a.dzs, a.nbb, a.xcd_remap ? a.G : -a.G, a);

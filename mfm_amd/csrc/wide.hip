@@ -1459,6 +1459,14 @@ struct FmCall {
   int* bad;              // non-null (training, one rank): finite check of the gradient rides in the weight-gradient kernel
 };
 // loss (+ gradient into d_grads, canonical layout) on `rows` samples; the per-workgroup loss partials land in w->loss_part
+// Grid of wgrad_kernel over `rows` rows: jobs [0, n_full) run one per wave, n_tail jobs a workgroup each.  The tail is what does not
+// fill the chip's 2048 wave slots a whole number of times, if it is at most one workgroup per CU and the rows split four ways.
+static void wgrad_grid(const Ctx* w, int rows, int& n_full, int& n_tail) {
+  const int rem = w->n_jobs % 2048;
+  const bool tail = w->n_jobs > 2048 && rem > 0 && rem <= 256 && rows % 64 == 0 && !g_sw.wide_wgrad_nosplit;
+  n_tail = tail ? rem : 0;
+  n_full = tail ? w->n_jobs - rem : (w->n_jobs + 3) / 4 * 4;
+}
 static int fm(Ctx* w, const NetDev& n, const FmCall& c, bool train, float* d_grads, hipStream_t s) {
   const int rows = c.rows;
   if (rows > w->R || rows % 16) return -3;
@@ -1521,11 +1529,9 @@ static int fm(Ctx* w, const NetDev& n, const FmCall& c, bool train, float* d_gra
   for (int i = 0; i <= jl; ++i) wg(w->lj[i], i == 0 ? w->catv : w->ja[i - 1], i == 0 ? w->cat : w->hj[i - 1], w->dja[i], w->hj[i]);
   wg(w->l_out, w->ja[jl], w->hj[jl], w->dv, n.dp);
   a.jobs = w->jobs; a.n_jobs = w->n_jobs; a.rows = rows; a.grads = d_grads; a.bad = c.bad;
-  // what does not fill the chip's 2048 wave slots a whole number of times, if it is a tail of at most one workgroup per CU
-  const int rem = w->n_jobs % 2048;
-  const bool tail = w->n_jobs > 2048 && rem > 0 && rem <= 256 && rows % 64 == 0 && !g_sw.wide_wgrad_nosplit;
-  a.n_full = tail ? w->n_jobs - rem : (w->n_jobs + 3) / 4 * 4;
-  hipLaunchKernelGGL(wgrad_kernel, dim3(a.n_full / 4 + (tail ? rem : 0)), dim3(256), 0, s, a);
+  int n_tail = 0;
+  wgrad_grid(w, rows, a.n_full, n_tail);
+  hipLaunchKernelGGL(wgrad_kernel, dim3(a.n_full / 4 + n_tail), dim3(256), 0, s, a);
   return 0;
 }
 

@@ -43,8 +43,14 @@ def flow_batch(key, samples, sigma, n_total=None, start=0):
 
 
 def loss_and_grad(model, params, key, samples, sigma, cond_flow=True, n_total=None, start=0,
-                  need_grad=True, ref_std=1.0):
-    """``exe_flow_matching.py:171-178`` + ``:364-365``."""
+                  need_grad=True, ref_std=1.0, abs_sums=False, operands=False):
+    """``exe_flow_matching.py:171-178`` + ``:364-365``.
+
+    ``abs_sums``: a third result, the ABSOLUTE-product sums of every gradient element in float64, laid out like the gradient:
+    ``S[layer]["kernel"][k, n] = sum over the chains of |a_k| |dz_n|`` and ``S[layer]["bias"][n] = sum of |dz_n|``, where the
+    gradient itself is ``sum a_k dz_n`` / ``sum dz_n``.  A float32 summation of B such products in ANY order is within
+    ``(B + 2) 2^-24 S`` of the exact sum: the yardstick of the summation-order tests.  ``operands``: a further result, the float64
+    factors themselves, a list of ``(A [B, in], dZ [B, out])`` per layer (``vfield.backward``)."""
     batch = cond_flow_batch if cond_flow else flow_batch
     t, cond, target = batch(key, samples, sigma, n_total, start, ref_std) if cond_flow else batch(key, samples, sigma, n_total, start)
     if not need_grad:
@@ -53,5 +59,17 @@ def loss_and_grad(model, params, key, samples, sigma, cond_flow=True, n_total=No
     v, cache = model.forward(params, cond, t, cache=True)
     diffs = v - target                                                               # :177
     loss = (diffs * diffs).sum()                                                     # :178
-    grads = model.backward(params, cache, 2.0 * diffs)
-    return loss, grads
+    if not (abs_sums or operands):
+        return loss, model.backward(params, cache, 2.0 * diffs)
+    grads, ops = model.backward(params, cache, 2.0 * diffs, operands=True)
+    out = [loss, grads]
+    if abs_sums:
+        out.append(abs_product_sums(ops))
+    if operands:
+        out.append(ops)
+    return tuple(out)
+
+
+def abs_product_sums(ops):
+    """``sum |a_k| |dz_n|`` (kernel) and ``sum |dz_n|`` (bias) over the chains, float64, for the ``(A, dZ)`` pairs of ``vfield.backward``."""
+    return [{"kernel": np.abs(A).T @ np.abs(dZ), "bias": np.abs(dZ).sum(0)} for A, dZ in ops]

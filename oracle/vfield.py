@@ -181,41 +181,43 @@ class VectorFieldNet:
             hd = hd * inside
         return tr + (nn_t * hd).sum(1)
 
-    def backward(self, params, cache, dv):
-        """Parameter gradients of sum(dv * v) given the forward cache; float32 like the params."""
+    def backward(self, params, cache, dv, operands=False):
+        """Parameter gradients of sum(dv * v) given the forward cache; float32 like the params.  ``operands``: also the float64
+        factors of every layer's gradient, a list of ``(A [B, in], dZ [B, out])`` with ``dW = A.T @ dZ`` and ``db = dZ.sum(0)``."""
         lt, lx, lxt = len(self.hidden_t), len(self.hidden_x), len(self.hidden_xt)
         acts_in, pre, g = cache
         W = [p["kernel"].astype(np.float64) for p in params]
         n = len(W)
-        dW, db = [None] * n, [None] * n
+        dW, db, dzs = [None] * n, [None] * n, [None] * n
         li = n - 1
         dz = dv                                                  # output layer
-        dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0)
+        dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0); dzs[li] = dz
         ds = dz @ W[li].T
         for k in range(lxt):                                     # joint branch, reversed
             li -= 1
             dz = ds * self.dact(pre[li])
-            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0)
+            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0); dzs[li] = dz
             ds = dz @ W[li].T
         hx = W[lt + lx - 1].shape[1] if lx else self.dim
         d_sx, d_st = ds[:, :hx], ds[:, hx:]
         li -= 1                                                  # gate layer
         dz = dv * g
-        dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0)
+        dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0); dzs[li] = dz
         d_st = d_st + dz @ W[li].T
         ds = d_sx
         for k in range(lx):                                      # x branch, reversed
             li -= 1
             dz = ds * self.dact(pre[li])
-            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0)
+            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0); dzs[li] = dz
             ds = dz @ W[li].T
         ds = d_st
         for k in range(lt):                                      # time branch, reversed
             li -= 1
             dz = ds * self.dact(pre[li])
-            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0)
+            dW[li] = acts_in[li].T @ dz; db[li] = dz.sum(0); dzs[li] = dz
             ds = dz @ W[li].T
-        return [{"kernel": dW[i].astype(np.float32), "bias": db[i].astype(np.float32)} for i in range(n)]
+        grads = [{"kernel": dW[i].astype(np.float32), "bias": db[i].astype(np.float32)} for i in range(n)]
+        return (grads, [(acts_in[i], dzs[i]) for i in range(n)]) if operands else grads
 
 
 def flat_params(params):
