@@ -432,6 +432,20 @@ int mfm_wsk_plan(int n_jobs, int nbb, int cap, int g_override, int32_t h_out[4],
  * h_out = {kind, n_jobs, nbb, G, q, r}.  kind 0: the slab kernels (G = n_jobs * split workgroups, slices of q or q + 1 tiles, r = nbb %
  * split); 1: stream-K (G, q, r as mfm_wsk_plan); 2: the wide family (G workgroups, q of them the workgroup-per-job tail, r = 0). */
 int mfm_wgrad_info(mfm_ctx* ctx, int32_t h_out[6]);
+/* Which GEMM instance the wide family (wide.hip: launch_gemm, which launches from the same function) runs for `rows` rows (a multiple of
+ * 16), KB 16-wide K blocks and NT 16-feature column tiles; dual != 0: a tangent GEMM over the first KBT K blocks rides along.  Needs
+ * no context and no GPU: `switches` is the OR of the MFM_WGEMM_SW_* bits of the development switches a context latches at mfm_create
+ * (MFM_WIDE_NOLDS, MFM_WIDE_NO_SMALL_TILES, MFM_WIDE_WM1, MFM_WIDE_RING8).  h_out = {instance (MFM_WGEMM_*), gridDim.x, gridDim.y,
+ * blockDim.x}.  The names say the kernel and the 16 x 16 tiles per wave (rows x features) of its 2 x 2 waves: 11 / 12 / 22 and BIG (4 x 2)
+ * are the register-only gemm_kernel (RING8: its ring of eight K blocks), LDS the LDS-staged kernel of eight waves (WM1: of four). */
+enum { MFM_WGEMM_11 = 0, MFM_WGEMM_11_DUAL = 1, MFM_WGEMM_12 = 2, MFM_WGEMM_12_DUAL = 3, MFM_WGEMM_22 = 4, MFM_WGEMM_22_DUAL = 5,
+       MFM_WGEMM_22_RING8 = 6, MFM_WGEMM_22_RING8_DUAL = 7, MFM_WGEMM_BIG = 8, MFM_WGEMM_LDS = 9, MFM_WGEMM_LDS_DUAL = 10,
+       MFM_WGEMM_LDS_WM1 = 11, MFM_WGEMM_LDS_WM1_DUAL = 12, MFM_WGEMM_COUNT = 13 };
+enum { MFM_WGEMM_SW_NOLDS = 1, MFM_WGEMM_SW_NO_SMALL_TILES = 2, MFM_WGEMM_SW_WM1 = 4, MFM_WGEMM_SW_RING8 = 8 };
+int mfm_wide_gemm_plan(int rows, int KB, int NT, int dual, int KBT, unsigned switches, int32_t h_out[4]);
+/* Launches of each instance by this context since it was created or last reset: h_out[MFM_WGEMM_COUNT], counted on the host where
+ * launch_gemm launches (no device work, no synchronisation).  reset != 0 zeroes the tally after the read; h_out may be NULL then. */
+int mfm_wide_gemm_tally(mfm_ctx* ctx, int64_t* h_out, int reset);
 
 #ifdef __cplusplus
 }

@@ -109,6 +109,8 @@ _SIGS = {
     "mfm_threefry2x32": (C.c_int, [_U32, _U32, _U32, _U32, C.POINTER(_U32)]),
     "mfm_wsk_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mfm_wgrad_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "mfm_wide_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int32)]),
+    "mfm_wide_gemm_tally": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -172,6 +174,18 @@ def wsk_plan(n_jobs, nbb, cap, g_override=0, ranges=True):
 
 
 WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2      # mfm_wgrad_info: kind
+
+# include/mfm.h: MFM_WGEMM_* (the instances of the wide family's GEMM, in enum order) and MFM_WGEMM_SW_* (its latched switches)
+WGEMM = ("11", "11_dual", "12", "12_dual", "22", "22_dual", "22_ring8", "22_ring8_dual", "big", "lds", "lds_dual", "lds_wm1", "lds_wm1_dual")
+WGEMM_SW = {"MFM_WIDE_NOLDS": 1, "MFM_WIDE_NO_SMALL_TILES": 2, "MFM_WIDE_WM1": 4, "MFM_WIDE_RING8": 8}
+
+
+def wide_gemm_plan(rows, KB, NT, dual=False, KBT=0, switches=0):
+    """``mfm_wide_gemm_plan`` (host only): ``(instance name from WGEMM, gridDim.x, gridDim.y, blockDim.x)`` of the wide family's GEMM
+    for this shape under the switch mask ``switches`` (OR of ``WGEMM_SW`` values)."""
+    out = (C.c_int32 * 4)()
+    _chk(load().mfm_wide_gemm_plan(int(rows), int(KB), int(NT), int(bool(dual)), int(KBT), int(switches), out))
+    return WGEMM[out[0]], out[1], out[2], out[3]
 
 
 class Context:
@@ -403,6 +417,13 @@ class Context:
         out = (C.c_int32 * 6)()
         _chk(self.lib.mfm_wgrad_info(self.h, out))
         return dict(zip(("kind", "n_jobs", "nbb", "G", "q", "r"), [int(v) for v in out]))
+
+    def wide_gemm_tally(self, reset=False):
+        """Launches of each wide-family GEMM instance by this context since its creation or last reset (``mfm_wide_gemm_tally``;
+        counted on the host): ``{name from WGEMM: launches}``."""
+        out = (C.c_int64 * len(WGEMM))()
+        _chk(self.lib.mfm_wide_gemm_tally(self.h, out, int(bool(reset))))
+        return dict(zip(WGEMM, [int(v) for v in out]))
 
     def adamw_step(self, grads):
         self._p()

@@ -105,12 +105,13 @@ struct mfm_ctx {
   int opt_resident_wgs = 0;              // workgroups of reduce_adamw_kernel this device holds at once (occupancy query at create)
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* run_ws = nullptr; size_t run_ws_cap = 0;   // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
+  mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
 };
 
 // The development switches (common.hip.h) are read once per mfm_create and belong to THAT context: every entry point installs its
 // context's snapshot before it sizes or launches anything, so a second context created under another environment cannot change what an
 // earlier one launches (its workspaces were sized from its own snapshot: e.g. the flow step's chains per workgroup, MFM_FLOW_LIVE).
-static inline void use_ctx(const mfm_ctx* x) { if (x) g_sw = x->sw; }
+static inline void use_ctx(const mfm_ctx* x) { if (x) { g_sw = x->sw; wide::g_gemm_tally = x->wgemm_tally; } }
 
 struct ProfScope {
   mfm_ctx* x; bool active;
@@ -402,6 +403,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
     delete w;
   }
   if (x->prof) { for (auto& e : x->prof->ev) (void)hipEventDestroy(e); delete x->prof; }
+  if (wide::g_gemm_tally == x->wgemm_tally) wide::g_gemm_tally = nullptr;
   delete x;
   return MFM_OK;
 }
@@ -1010,6 +1012,20 @@ extern "C" int mfm_wgrad_info(mfm_ctx* x, int32_t h_out[6]) { use_ctx(x);
   } else {
     h_out[0] = 0; h_out[1] = x->n_jobs; h_out[2] = nbb; h_out[3] = x->n_jobs * x->split; h_out[4] = nbb / x->split; h_out[5] = nbb % x->split;
   }
+  return MFM_OK;
+}
+extern "C" int mfm_wide_gemm_plan(int rows, int KB, int NT, int dual, int KBT, unsigned switches, int32_t h_out[4]) {
+  if (!h_out) return fail(MFM_EINVAL, "mfm_wide_gemm_plan: h_out is null");
+  if (rows < 16 || rows % 16 || KB < 1 || NT < 1) return fail(MFM_EINVAL, "mfm_wide_gemm_plan: rows=%d KB=%d NT=%d (rows a positive multiple of 16, KB and NT positive)", rows, KB, NT);
+  if (dual && (KBT < 1 || KBT > KB)) return fail(MFM_EINVAL, "mfm_wide_gemm_plan: KBT=%d outside [1, KB=%d]", KBT, KB);
+  if (switches & ~15u) return fail(MFM_EINVAL, "mfm_wide_gemm_plan: unknown switch bits 0x%x", switches);
+  const wide::GemmPlan p = wide::gemm_plan(rows, KB, NT, dual != 0, dual ? KBT : 0, switches);
+  h_out[0] = p.inst; h_out[1] = p.gx; h_out[2] = p.gy; h_out[3] = p.block;
+  return MFM_OK;
+}
+extern "C" int mfm_wide_gemm_tally(mfm_ctx* x, int64_t* h_out, int reset) { use_ctx(x);
+  if (!x || (!h_out && !reset)) return fail(MFM_EINVAL, "mfm_wide_gemm_tally: null argument");
+  for (int i = 0; i < MFM_WGEMM_COUNT; ++i) { if (h_out) h_out[i] = x->wgemm_tally[i]; if (reset) x->wgemm_tally[i] = 0; }
   return MFM_OK;
 }
 extern "C" int mfm_fm_eval_instance(mfm_ctx* x, int n) { use_ctx(x);

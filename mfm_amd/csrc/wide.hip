@@ -363,52 +363,65 @@ __global__ __launch_bounds__(256 * WM) void gemm_lds_kernel(Gemm a) {
   gemm_epilogue<MTW, 1>(a, acc, acT, mt0, nt, MT, g, c);
 }
 
-static void launch_gemm(const Gemm& a, hipStream_t s) {
-  const bool dual = a.XT != nullptr;
-  const int MT = a.rows / 16;
+// Which instance serves a GEMM of `rows` rows, KB K blocks, NT feature tiles (dual: a tangent GEMM over the first KBT K blocks rides
+// along), and on which grid: a pure function of the shape and the latched switches (`sw`: MFM_WGEMM_SW_*).  launch_gemm launches
+// from it and mfm_wide_gemm_plan reports it, so a test can assert the instance it claims to run.
+struct GemmPlan { int inst; int gx, gy, block; };
+static GemmPlan gemm_plan(int rows, int KB, int NT, bool dual, int KBT, unsigned sw) {
+  const int MT = rows / 16;
   // 2 x 2 waves per workgroup; wave tile (16 MTW) rows x (16 NTW) features.  Small problems (this path runs ~1024 rows)
   // take the 32 x 32 wave tile so that the launch still covers the 1024 SIMDs.
   // tall launches (the batched time branch: 5 x rows) without whole 128-wide K steps keep round 1's 128 x 64 register-only tile;
   // wherever the LDS-staged kernel applies it is the faster one at every height (pines flow step 54.4 -> 51.8 ms when the batched
   // time-branch GEMMs moved to it)
-  const bool no_lds_any = g_sw.wide_nolds;
-  const bool big = (long long)MT * a.NT >= 4 * 4096 && !dual && (no_lds_any || (a.KB & 7) != 0);
-  if (big) {
-    dim3 grid((a.NT + 3) / 4, (MT + 7) / 8);
-    hipLaunchKernelGGL((gemm_kernel<4, 2, false>), grid, dim3(256), 0, s, a);
-  } else if (a.rows <= 512 && !g_sw.wide_no_small_tiles) {
+  const bool no_lds = (sw & MFM_WGEMM_SW_NOLDS) != 0;
+  const bool big = (long long)MT * NT >= 4 * 4096 && !dual && (no_lds || (KB & 7) != 0);
+  if (big) return GemmPlan{MFM_WGEMM_BIG, (NT + 3) / 4, (MT + 7) / 8, 256};
+  if (rows <= 512 && !(sw & MFM_WGEMM_SW_NO_SMALL_TILES)) {
     // few rows (the compacted attempts of a solve's tail, small batches): with 64 x 64 workgroup tiles a 256-row layer is 64
     // workgroups on 256 CUs and lasts as long as the 1024-row one.  Smaller tiles of the register-only kernel keep the chip
     // covered: 32 rows x 64 features up to 512 rows, 32 x 32 up to 256.
-    if (a.rows <= 256) {
-      dim3 grid((a.NT + 1) / 2, (MT + 1) / 2);
-      if (dual) hipLaunchKernelGGL((gemm_kernel<1, 1, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_kernel<1, 1, false>), grid, dim3(256), 0, s, a);
-    } else {
-      dim3 grid((a.NT + 3) / 4, (MT + 1) / 2);
-      if (dual) hipLaunchKernelGGL((gemm_kernel<1, 2, true>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_kernel<1, 2, false>), grid, dim3(256), 0, s, a);
-    }
-  } else {
-    dim3 grid((a.NT + 3) / 4, (MT + 3) / 4);
-    // the LDS-staged kernel needs an even number of whole 64-wide K steps (every width of the reference's pines networks); MFM_WIDE_NOLDS=1
-    // keeps the register-only kernel for A/B measurements
-    const bool no_lds = g_sw.wide_nolds;
-    const bool lds = !no_lds && (a.KB & 7) == 0 && (!dual || ((a.KBT & 3) == 0 && a.KBT >= 4));
-    const bool wm2 = !g_sw.wide_wm1;    // eight waves (two per SIMD) by default: 37.0 k vs 40.6 k cycles on 1024^3
-    if (lds && wm2) {
-      if (dual) hipLaunchKernelGGL((gemm_lds_kernel<true, 2>), grid, dim3(512), 0, s, a);
-      else hipLaunchKernelGGL((gemm_lds_kernel<false, 2>), grid, dim3(512), 0, s, a);
-    } else if (lds) {
-      if (dual) hipLaunchKernelGGL((gemm_lds_kernel<true, 1>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_lds_kernel<false, 1>), grid, dim3(256), 0, s, a);
-    } else if (dual) {
-      if (a.KB % 8 == 0 && a.KBT % 8 == 0 && g_sw.wide_ring8) hipLaunchKernelGGL((gemm_kernel<2, 2, true, 8>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_kernel<2, 2, true>), grid, dim3(256), 0, s, a);
-    } else {
-      if (a.KB % 8 == 0 && g_sw.wide_ring8) hipLaunchKernelGGL((gemm_kernel<2, 2, false, 8>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_kernel<2, 2, false>), grid, dim3(256), 0, s, a);
-    }
+    if (rows <= 256) return GemmPlan{dual ? MFM_WGEMM_11_DUAL : MFM_WGEMM_11, (NT + 1) / 2, (MT + 1) / 2, 256};
+    return GemmPlan{dual ? MFM_WGEMM_12_DUAL : MFM_WGEMM_12, (NT + 3) / 4, (MT + 1) / 2, 256};
+  }
+  // the LDS-staged kernel needs an even number of whole 64-wide K steps (every width of the reference's pines networks); MFM_WIDE_NOLDS=1
+  // keeps the register-only kernel for A/B measurements
+  const bool lds = !no_lds && (KB & 7) == 0 && (!dual || ((KBT & 3) == 0 && KBT >= 4));
+  const bool wm2 = !(sw & MFM_WGEMM_SW_WM1);    // eight waves (two per SIMD) by default: 37.0 k vs 40.6 k cycles on 1024^3
+  const bool ring8 = (sw & MFM_WGEMM_SW_RING8) && KB % 8 == 0 && (!dual || KBT % 8 == 0);
+  int inst;
+  if (lds && wm2) inst = dual ? MFM_WGEMM_LDS_DUAL : MFM_WGEMM_LDS;
+  else if (lds) inst = dual ? MFM_WGEMM_LDS_WM1_DUAL : MFM_WGEMM_LDS_WM1;
+  else if (ring8) inst = dual ? MFM_WGEMM_22_RING8_DUAL : MFM_WGEMM_22_RING8;
+  else inst = dual ? MFM_WGEMM_22_DUAL : MFM_WGEMM_22;
+  return GemmPlan{inst, (NT + 3) / 4, (MT + 3) / 4, lds && wm2 ? 512 : 256};
+}
+static unsigned gemm_switch_mask() {
+  return (g_sw.wide_nolds ? MFM_WGEMM_SW_NOLDS : 0u) | (g_sw.wide_no_small_tiles ? MFM_WGEMM_SW_NO_SMALL_TILES : 0u) |
+         (g_sw.wide_wm1 ? MFM_WGEMM_SW_WM1 : 0u) | (g_sw.wide_ring8 ? MFM_WGEMM_SW_RING8 : 0u);
+}
+// launches per instance of the context whose entry point is running (api.hip: use_ctx installs it; mfm_wide_gemm_tally reads it): host side only
+static int64_t* g_gemm_tally = nullptr;
+
+static void launch_gemm(const Gemm& a, hipStream_t s) {
+  const bool dual = a.XT != nullptr;
+  const GemmPlan p = gemm_plan(a.rows, a.KB, a.NT, dual, a.KBT, gemm_switch_mask());
+  const dim3 grid(p.gx, p.gy), block(p.block);
+  if (g_gemm_tally) g_gemm_tally[p.inst] += 1;
+  switch (p.inst) {
+    case MFM_WGEMM_BIG: hipLaunchKernelGGL((gemm_kernel<4, 2, false>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_11: hipLaunchKernelGGL((gemm_kernel<1, 1, false>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_11_DUAL: hipLaunchKernelGGL((gemm_kernel<1, 1, true>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_12: hipLaunchKernelGGL((gemm_kernel<1, 2, false>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_12_DUAL: hipLaunchKernelGGL((gemm_kernel<1, 2, true>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_LDS: hipLaunchKernelGGL((gemm_lds_kernel<false, 2>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_LDS_DUAL: hipLaunchKernelGGL((gemm_lds_kernel<true, 2>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_LDS_WM1: hipLaunchKernelGGL((gemm_lds_kernel<false, 1>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_LDS_WM1_DUAL: hipLaunchKernelGGL((gemm_lds_kernel<true, 1>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_22_RING8: hipLaunchKernelGGL((gemm_kernel<2, 2, false, 8>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_22_RING8_DUAL: hipLaunchKernelGGL((gemm_kernel<2, 2, true, 8>), grid, block, 0, s, a); break;
+    case MFM_WGEMM_22_DUAL: hipLaunchKernelGGL((gemm_kernel<2, 2, true>), grid, block, 0, s, a); break;
+    default: hipLaunchKernelGGL((gemm_kernel<2, 2, false>), grid, block, 0, s, a); break;
   }
 }
 
