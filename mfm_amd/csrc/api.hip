@@ -814,7 +814,7 @@ extern "C" int mfm_loglik(mfm_ctx* x, const float* d_pos, double* d_out) { use_c
   if (!d_pos || !d_out) return fail(MFM_EINVAL, "null device pointer");
   MalaArgs a = mala_args(x, 1.0);
   a.pos = const_cast<float*>(d_pos);
-  if (launch_loglik(a, d_out, x->stream)) return fail(MFM_ETOOLARGE, "dim %d too large", x->cfg.dim);
+  if (launch_loglik(a, d_out, x->stream)) return too_large(x, "loglik");
   LAUNCHCHK();
   return MFM_OK;
 }

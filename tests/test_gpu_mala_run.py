@@ -2,7 +2,7 @@
 
 The yardstick is the single-step kernel: a run of n steps must give the BITS of n launches of ``mfm_mala_step`` /
 ``mfm_mala_step_keys`` on the step keys the run derives (step-major: ``split(key, n)[j]``; chain-major: ``split_rows(keys, n)[:, j]``),
-for every kernel instance (MAXIT 1 / 4, the run-time boundary instances, the mixture path), plus one comparison with the float64 oracle
+for every kernel instance (MAXIT 1 / 4 / 16 / 32, each with the run-time boundary, the mixture path), plus one comparison with the float64 oracle
 at the tolerances stated for the MALA tests (docs/HISTORY.md section 2), the Cox process (a loop of its tile step inside the library),
 the SMC move that uses the run, the Python API and the argument errors.
 
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import mala as omala, prng, targets
+from tests import row_instance_cases as rc
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +32,21 @@ CASES = {
     "phi4_d64_beta03": ("phi4", 64, None, 0.3, 2.5e-4, False),
     "gmm4_textbook": ("gmm", 2, None, 1.0, 1.5, True),
 }
+# The dispatch instances above d = 256 (and MAXIT 4 with a run-time boundary), which tie mala_run_kernel and the warmup kernel there to the
+# step kernel that tests/test_gpu_row_instances.py holds to the oracle: target "row", the case of tests/row_instance_cases.py in the place
+# of d -- its start state near a mode (16 chains), its boundary and its step sizes (beta = 1 as written; beta = 0.37 textbook, which the
+# warmup tests take), ROW_STEPS steps.  Oracle means of the acceptance probability over the 5 steps: 0.45 ... 0.75 as written, 0.33 ...
+# 0.67 textbook.  (MAXIT, BCRT): d65_pbc (4, true), d257_d0 (16, false), 17x17_pbc (16, true), d2048_d0 (32, false), d1025_pbc and
+# 33x33_db (32, true).
+ROW_STEPS = 5
+ROW_CASES = ("d65_pbc", "d257_d0", "17x17_pbc", "d2048_d0", "d1025_pbc", "33x33_db")
+for _c in ROW_CASES:
+    CASES["row_" + _c] = ("row", _c, None, 1.0, rc.STEP_SIZES[_c]["mala"]["b1"], False)
+    CASES["row_" + _c + "_textbook"] = ("row", _c, None, 0.37, rc.STEP_SIZES[_c]["mala"]["b037_textbook"], True)
+
+
+def _n_steps(case):
+    return ROW_STEPS if CASES[case][0] == "row" else N_STEPS
 
 
 def _ctx(kind, d, tail, n=B):
@@ -38,6 +54,12 @@ def _ctx(kind, d, tail, n=B):
     import torch
     from mfm_amd import _lib
     from tests import gpu_util as gu
+    if kind == "row":                               # d: a case of tests/row_instance_cases.py, with its own chains and start state
+        args, dist0, *_ = gu.phi4_setup(d=rc.CASES[d][0], B=rc.N_CHAINS, hidden=32, F=16)
+        ctx = gu.make_ctx(dist0, args)
+        if rc.block(d) is not None:
+            ctx.set_target(_lib.PHI4, rc.block(d))
+        return ctx, torch.as_tensor(rc.start_state(d)).cuda(), rc.oracle_dist(d)
     if kind == "phi4":
         args, dist, k, model, state = gu.phi4_setup(d=d, B=n, hidden=32, F=16)
     elif kind == "gmm":
@@ -126,8 +148,8 @@ def test_run_is_bit_identical_with_single_step_launches(case):
     ctx, pos0, _ = _ctx(kind, d, tail)
     state0 = _init(ctx, pos0, beta)
     key = prng.PRNGKey(21)
-    steps = _stepwise(ctx, state0, key, beta, eps, N_STEPS, textbook)
-    run = _run(ctx, state0, key, beta, eps, N_STEPS, 1, textbook)
+    steps = _stepwise(ctx, state0, key, beta, eps, _n_steps(case), textbook)
+    run = _run(ctx, state0, key, beta, eps, _n_steps(case), 1, textbook)
     _assert_run_equals_steps(run, steps)
     ctx.close()
 
@@ -166,17 +188,30 @@ def test_thinning_and_no_trajectory():
 ORACLE_SEED = 4      # the first seed whose 80 decisions all have |u - p| > 1e-2 in the float64 oracle (asserted below)
 
 
+ORACLE_SEED_D1025 = 0      # the first seed with the same property for the d = 1025 periodic case
+
+
 def test_run_matches_the_float64_oracle():
     """phi-four d = 64, 16 chains, 5 steps from ``oracle.mala.init``: the oracle's kernel looped over split(key, 5)[j] -> split(., 16).
     Tolerances of the MALA tests (docs/HISTORY.md section 2; the several-step forms of tests/test_gpu_mala_api.py): proposal 1e-6,
     acceptance probability 5e-3, decisions identical -- every chain: the seed keeps all 80 decisions off the knife edge."""
+    _run_against_the_oracle("phi4", 64, 4e-5, ORACLE_SEED)
+
+
+def test_run_matches_the_float64_oracle_at_d1025():
+    """The same comparison on the MAXIT 32 run-time-boundary instance: the periodic chain of d = 1025 from its start state near a mode
+    (tests/row_instance_cases.py), at that table's step size."""
+    _run_against_the_oracle("row", "d1025_pbc", rc.STEP_SIZES["d1025_pbc"]["mala"]["b1"], ORACLE_SEED_D1025)
+
+
+def _run_against_the_oracle(kind, d, eps, seed):
     import torch
-    n, d, n_steps, beta, eps = 16, 64, 5, 1.0, 4e-5
-    ctx, pos0, dist = _ctx("phi4", d, None, n=n)
+    n, n_steps, beta = 16, 5, 1.0
+    ctx, pos0, dist = _ctx(kind, d, None, n=n)
     vg = targets.Tempered(dist, beta).value_and_grad
     st = omala.init(pos0.cpu().numpy().astype(np.float64), vg)
     state0 = (pos0.clone(), torch.as_tensor(st.logdensity).cuda(), torch.as_tensor(st.logdensity_grad.astype(np.float32)).cuda())
-    key = prng.PRNGKey(ORACLE_SEED)
+    key = prng.PRNGKey(seed)
     o_pos, o_logp, o_p, o_acc, margin = [], [], [], [], []
     for j in range(n_steps):
         st, info, u = omala.kernel(prng.split(prng.split(key, n_steps)[j], n), st, vg, eps)

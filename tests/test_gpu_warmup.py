@@ -113,7 +113,12 @@ def _assert_warmup_equals_replay(w, rep, step0, target):
     return mixed, parted
 
 
-@pytest.mark.parametrize("case", ["phi4_d64", "phi4_d100", "phi4_d256", "phi4_d64_pbc", "gmm4"])
+# the "row_" cases: the warmup kernels on the dispatch instances above d = 256 and on MAXIT 4 with a run-time boundary (the tables of
+# tests/test_gpu_hmc_run.py and tests/test_gpu_mala_run.py; start states near a mode, where the chains' step sizes part at the second step)
+ROW = ["row_d65_pbc", "row_d257_d0", "row_17x17_pbc", "row_d2048_d0", "row_d1025_pbc", "row_33x33_db"]
+
+
+@pytest.mark.parametrize("case", ["phi4_d64", "phi4_d100", "phi4_d256", "phi4_d64_pbc", "gmm4"] + ROW)
 def test_hmc_warmup_replays_as_single_steps_and_follows_the_recursion(case):
     kind, d, tail, beta, step0 = HMC_CASES[case]
     ctx, pos0, _ = _ctx(kind, d, tail)
@@ -139,11 +144,14 @@ def test_hmc_warmup_chain_major_keys():
 
 # (case, steps, whether the chains' step sizes part within those steps: module docstring)
 MALA_RUNS = [("phi4_d64", N_STEPS, True), ("phi4_d256", N_STEPS, False), ("phi4_d256", 20, True), ("gmm4", N_STEPS, True)]
+# (the MAXIT 1 run-time-boundary instance: as d = 256 at 8 steps, every chain's p is 0 or 1 until the eighth step of the restatement)
+MALA_RUNS += [("phi4_d64_pbc", N_STEPS, False)] + [(c + "_textbook", N_STEPS, True) for c in ROW]
 
 
 @pytest.mark.parametrize("case,n_steps,parts", MALA_RUNS, ids=[f"{c}-{n}" for c, n, _ in MALA_RUNS])
 def test_mala_warmup_replays_as_single_steps_and_follows_the_recursion(case, n_steps, parts):
-    """phi-four d = 64 (MAXIT 1), d = 256 (MAXIT 4) and the 4-mode mixture under the textbook rule."""
+    """phi-four d = 64 (MAXIT 1), d = 256 (MAXIT 4) and the 4-mode mixture under the textbook rule; the periodic d = 64 chain and the
+    "row_" cases (MAXIT 4 with a run-time boundary, MAXIT 16 and 32 with and without)."""
     kind, d, tail, beta, step0, _ = MALA_CASES[case]
     ctx, pos0, _ = _ctx(kind, d, tail)
     state0 = _init(ctx, pos0, beta)
