@@ -218,6 +218,29 @@ int mfm_mala_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, co
                     double* d_step_avg, double* d_step_last,
                     int32_t* d_n_accepted, double* d_acc_sum,
                     double* d_step_traj);
+/* DIAGONAL MASS MATRIX of the HMC entry points (blackjax's inverse_mass_matrix as a vector).  h_inv_mass is a HOST vector, the diagonal
+ * minv of M^-1.  With it a step draws the momentum p_j = n_j / sqrt(minv_j) from the same normal draws n_j, has the energy
+ * H = -logp + sum_j minv_j p_j^2 / 2, and drifts by x_j += step_size * minv_j * p_j; kicks and the accept rule are unchanged.
+ * n == dim installs the vector on the context: every later mfm_hmc_step, mfm_hmc_step_keys, mfm_hmc_run and mfm_hmc_warmup call runs the
+ * mass instances of its kernel with it (a vector of ones gives, bit for bit, what the call gives with none installed).  n == 0 with
+ * h_inv_mass == NULL returns to unit mass and the unit instances.  Any other n, or an entry that is not finite and positive, returns
+ * MFM_EINVAL naming inv_mass, and the context keeps what it had.  The call waits for the context's stream.
+ * mfm_hmc_get_inverse_mass: h_out double[dim] (or NULL) takes the installed vector, ones when none is; *h_is_set (or NULL) 1 or 0. */
+int mfm_hmc_set_inverse_mass(mfm_ctx* ctx, const double* h_inv_mass, int32_t n);
+int mfm_hmc_get_inverse_mass(mfm_ctx* ctx, double* h_out /* [dim] */, int32_t* h_is_set);
+/* ONE WINDOW of a mass-matrix adaptation: mfm_hmc_warmup, which also leaves the sums a variance estimate needs in place of a trajectory.
+ * After every step the chain's state after accept / reject, the float32 position as a double, is added in step order to
+ * d_pos_sum double[B][dim] and its (exact) square to d_pos_sumsq double[B][dim]; both are required and are overwritten.  It always runs
+ * the mass instances, with the context's vector, or with ones when none is installed: everything else it writes then has
+ * mfm_hmc_warmup's bits.  Arguments and errors otherwise as mfm_hmc_warmup. */
+int mfm_hmc_warmup_window(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                          double beta, double step0, int32_t num_steps /* leapfrog steps per HMC step */,
+                          int32_t n_steps, double target_accept,
+                          float* d_pos, double* d_logp, float* d_grad,
+                          double* d_step_avg, double* d_step_last,
+                          int32_t* d_n_accepted, double* d_acc_sum,
+                          double* d_step_traj,
+                          double* d_pos_sum, double* d_pos_sumsq);
 /* vmap(dist.loglik) (exe_flow_matching.py:418) */
 int mfm_loglik(mfm_ctx* ctx, const float* d_pos, double* d_out);
 

@@ -68,6 +68,9 @@ _SIGS = {
     "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_hmc_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_mala_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_hmc_set_inverse_mass": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),
+    "mfm_hmc_get_inverse_mass": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "mfm_hmc_warmup_window": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_loglik": (C.c_int, [_P, _P, _P]),
     "mfm_smc_delta": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "mfm_smc_weights": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, C.POINTER(C.c_double)]),
@@ -346,6 +349,46 @@ class Context:
         _chk(self.lib.mfm_hmc_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
                                      int(num_steps), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                      _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
+
+    _inv_mass = None      # host copy of the installed vector (None: unit mass), what set_inverse_mass compares with
+
+    def set_inverse_mass(self, inv_mass=None):
+        """``mfm_hmc_set_inverse_mass``: install the diagonal ``inv_mass`` (``[dim]`` float64, finite and positive) of the inverse mass
+        matrix for every later ``hmc_step`` / ``hmc_step_keys`` / ``hmc_run`` / ``hmc_warmup`` call; ``None`` returns to unit mass.  The
+        context keeps a host copy and makes no call when nothing changes."""
+        if inv_mass is None:
+            if self._inv_mass is not None:
+                _chk(self.lib.mfm_hmc_set_inverse_mass(self.h, None, 0))
+                self._inv_mass = None
+            return
+        v = np.ascontiguousarray(inv_mass, dtype=np.float64).reshape(-1)
+        if self._inv_mass is not None and v.shape == self._inv_mass.shape and np.array_equal(v, self._inv_mass):
+            return
+        _chk(self.lib.mfm_hmc_set_inverse_mass(self.h, v.ctypes.data_as(C.POINTER(C.c_double)), v.size))
+        self._inv_mass = v.copy()
+
+    def get_inverse_mass(self):
+        """``mfm_hmc_get_inverse_mass``: ``(vector [dim] as the library holds it -- ones when none is installed --, whether one is)``."""
+        out, is_set = np.empty(self.dim, dtype=np.float64), C.c_int32(0)
+        _chk(self.lib.mfm_hmc_get_inverse_mass(self.h, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(is_set)))
+        return out, bool(is_set.value)
+
+    def hmc_warmup_window(self, key, beta, step0, num_steps, n_steps, target_accept, pos, logp, grad, step_avg, pos_sum, pos_sumsq,
+                          step_last=None, n_acc=None, acc_sum=None, step_traj=None, key_mode=None):
+        """``mfm_hmc_warmup_window``: ``hmc_warmup`` on the mass instances (the installed vector, or ones), which also leaves in
+        ``pos_sum`` / ``pos_sumsq`` (float64 ``[n_chain_local, dim]``, both required) the sums over the steps of every chain's position
+        after accept / reject and of its square: what a window of a mass-matrix adaptation needs in place of a trajectory."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        self._warmup_sizes(n_steps, step_avg, step_last, n_acc, acc_sum, step_traj)
+        for name, t_ in (("pos_sum", pos_sum), ("pos_sumsq", pos_sumsq)):
+            if t_ is not None and t_.numel() < self.n_local * self.dim:
+                raise MfmError(f"{name} must hold n_chain_local * dim = {self.n_local * self.dim} elements (got {t_.numel()})")
+        _chk(self.lib.mfm_hmc_warmup_window(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
+                                            int(num_steps), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                            _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64),
+                                            _ptr(pos_sum, F64), _ptr(pos_sumsq, F64)))
 
     def mala_warmup(self, key, beta, step0, n_steps, target_accept, pos, logp, grad, step_avg, step_last=None, n_acc=None,
                     acc_sum=None, step_traj=None, textbook=True, key_mode=None):

@@ -4,7 +4,11 @@ BASELINE.json's north star names a "MALA/HMC log-density-and-grad step"; the ref
 ``bblackjax/mcmc`` has no ``hmc.py`` (SURVEY.md note 7), so this module has no counterpart to be a drop-in for.  It follows the kernel of
 blackjax (the package ``bblackjax`` was cut from) with the same conventions as ``mala.py`` here: ``state.position`` is
 ``[n_chain_local, dim]`` (CUDA float32), ``rng_key`` the key BEFORE the per-chain split, ``logdensity_fn`` built from a device target;
-unit mass matrix, velocity Verlet, acceptance ``min(1, exp(H_0 - H_end))`` (``oracle/hmc.py``; device: ``mfm_hmc_step``).  As in
+velocity Verlet, acceptance ``min(1, exp(H_0 - H_end))`` (``oracle/hmc.py``; device: ``mfm_hmc_step``); unit mass matrix unless
+``inverse_mass_matrix`` is given: a vector ``[dim]``, the DIAGONAL of blackjax's ``inverse_mass_matrix`` (momentum
+``n / sqrt(minv)``, kinetic energy ``sum(minv p^2) / 2``, drift ``eps minv p``; ``mfm_hmc_set_inverse_mass``).  A call's mass is its
+argument, never what an earlier call left on the context: every launch installs or clears it first (the context keeps a host copy and
+uploads only a change).  ``adaptation/window_adaptation.py`` estimates one.  As in
 ``mala.py``, a caller that vmaps over its OWN keys passes ``rng_key`` of shape ``[n_chain_local, 2]`` (``mfm_hmc_step_keys``), and the
 kernel carries ``kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin=0)``: ``num_steps`` HMC
 steps in ONE launch (``mfm_hmc_run``) with the chain resident on the device between steps, and ``kernel.warmup(rng_key, state,
@@ -19,7 +23,24 @@ from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 from .mala import MALAState as HMCState, _engine, init
 
-__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "HMCWarmupInfo", "init", "build_kernel", "hmc"]
+__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "HMCWarmupInfo", "init", "build_kernel", "hmc", "check_inverse_mass"]
+
+
+def check_inverse_mass(inverse_mass_matrix, dim=None):
+    """``None``, or the diagonal as a float64 vector; ``ValueError`` for anything that is not a vector of ``dim`` finite, positive
+    entries (before any device work)."""
+    if inverse_mass_matrix is None:
+        return None
+    if hasattr(inverse_mass_matrix, "detach"):
+        inverse_mass_matrix = inverse_mass_matrix.detach().cpu().numpy()
+    v = np.array(inverse_mass_matrix, dtype=np.float64)
+    if v.ndim != 1:
+        raise ValueError(f"inverse_mass_matrix must be a vector, the diagonal (got shape {v.shape}); dense mass matrices are not served")
+    if dim is not None and v.size != int(dim):
+        raise ValueError(f"inverse_mass_matrix must have dim = {int(dim)} entries (got {v.size})")
+    if not (np.isfinite(v) & (v > 0)).all():
+        raise ValueError("inverse_mass_matrix: every entry must be finite and positive")
+    return v
 
 
 class HMCInfo(NamedTuple):
@@ -75,12 +96,20 @@ def _device_keys(t, rng_key, dev):
     return rng_key if t.is_tensor(rng_key) else t.as_tensor(np.ascontiguousarray(rng_key, dtype=np.uint32).view(np.int32), device=dev)
 
 
+def _mass_engine(dist, inverse_mass_matrix):
+    """The engine of ``dist`` with this call's mass installed on (or cleared from) its context."""
+    minv = check_inverse_mass(inverse_mass_matrix, getattr(dist, "dim", None))
+    eng = _engine(dist)
+    eng.ctx.set_inverse_mass(minv)
+    return eng
+
+
 def build_kernel():
-    def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int):
+    def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, inverse_mass_matrix=None):
         """One key: chain b draws from ``split(rng_key, n_chain_total)[chain_offset + b]``; keys ``[n_chain_local, 2]``: the caller's
         own vmap, chain b draws from ``rng_key[b]``."""
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _engine(dist)
+        eng = _mass_engine(dist, inverse_mass_matrix)
         t = eng.torch
         pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()      # states are values
         acc = t.empty(pos.shape[0], device=pos.device, dtype=t.float32)
@@ -91,12 +120,13 @@ def build_kernel():
             eng.ctx.hmc_step(rng_key, beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
         return HMCState(pos, logp, grad), HMCInfo(acc, isacc.bool())
 
-    def run(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int, thin: int = 0):
+    def run(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int, thin: int = 0,
+            inverse_mass_matrix=None):
         """``num_steps`` calls of ``kernel`` in one: with ONE key step j uses ``split(rng_key, num_steps)[j]`` (the scan of
         ``inference_loop0``); with keys ``[n_chain_local, 2]`` step j of chain b uses ``split(rng_key[b], num_steps)[j]``.
         Bit-identical with that loop.  ``thin >= 1`` keeps the state after every ``thin``-th step."""
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _engine(dist)
+        eng = _mass_engine(dist, inverse_mass_matrix)
         t = eng.torch
         num_steps, thin = int(num_steps), int(thin)
         pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()
@@ -116,12 +146,12 @@ def build_kernel():
         return HMCState(pos, logp, grad), HMCRunInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp)
 
     def warmup(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int,
-               target_acceptance_rate: float = 0.8, keep_step_sizes: bool = False):
+               target_acceptance_rate: float = 0.8, keep_step_sizes: bool = False, inverse_mass_matrix=None):
         """``num_steps`` HMC steps in one launch, from ``step_size``, every chain adapting its own step size towards
         ``target_acceptance_rate``; keys as ``run``'s (one key: step-major; ``[n_chain_local, 2]``: chain-major).  Returns the state
         after the steps and an ``HMCWarmupInfo``; ``info.pooled_step_size`` is the value to sample with."""
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _engine(dist)
+        eng = _mass_engine(dist, inverse_mass_matrix)
         return _warmup(lambda key, pos, logp, grad, **out: eng.ctx.hmc_warmup(key, beta, step_size, num_integration_steps, int(num_steps),
                                                                               target_acceptance_rate, pos, logp, grad, **out),
                        eng, rng_key, state, num_steps, keep_step_sizes)
@@ -135,20 +165,21 @@ class hmc:
     init = staticmethod(init)
     build_kernel = staticmethod(build_kernel)
 
-    def __new__(cls, logdensity_fn: Callable, step_size: float, num_integration_steps: int) -> SamplingAlgorithm:
+    def __new__(cls, logdensity_fn: Callable, step_size: float, num_integration_steps: int, inverse_mass_matrix=None) -> SamplingAlgorithm:
         kernel = cls.build_kernel()
+        minv = check_inverse_mass(inverse_mass_matrix, getattr(resolve_logdensity(logdensity_fn)[0], "dim", None))
 
         def init_fn(position):
             return cls.init(position, logdensity_fn)
 
         def step_fn(rng_key, state):
-            return kernel(rng_key, state, logdensity_fn, step_size, num_integration_steps)
+            return kernel(rng_key, state, logdensity_fn, step_size, num_integration_steps, minv)
 
         def run_fn(rng_key, state, num_steps, thin=0):
-            return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin)
+            return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin, minv)
 
         def warmup_fn(rng_key, state, num_steps, target_acceptance_rate=0.8, keep_step_sizes=False):
-            return kernel.warmup(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate, keep_step_sizes)
+            return kernel.warmup(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate, keep_step_sizes, minv)
 
         step_fn.run = run_fn
         step_fn.warmup = warmup_fn

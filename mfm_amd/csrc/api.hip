@@ -106,6 +106,10 @@ struct mfm_ctx {
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* run_ws = nullptr; size_t run_ws_cap = 0;   // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
   mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
+  // mfm_hmc_set_inverse_mass: the diagonal of the HMC kernels' inverse mass matrix.  d_inv_mass [dim] holds the installed vector, or
+  // ones when none is set (mfm_hmc_warmup_window runs the mass instances either way); h_inv_mass is the host copy, empty when none is set
+  double* d_inv_mass = nullptr;
+  std::vector<double> h_inv_mass;
 };
 
 // The development switches (common.hip.h) are read once per mfm_create and belong to THAT context: every entry point installs its
@@ -391,7 +395,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->d_inv_mass};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -697,7 +701,40 @@ static HmcArgs hmc_args(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_
   a.T = x->net.T; a.key = Key2{k0, k1}; a.keys = d_keys; a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local;
   a.num_steps = num_steps; a.beta = beta; a.eps = step;
   a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.acc_prob = d_acc; a.accepted = d_isacc;
+  a.minv = x->h_inv_mass.empty() ? nullptr : x->d_inv_mass;      // (set: the mass instances)
   return a;
+}
+
+// The diagonal of the inverse mass matrix of every later HMC call of this context (hmc.hip).  A rejected call changes nothing.
+static int inv_mass_upload(mfm_ctx* x, const std::vector<double>& h) {
+  if (!x->d_inv_mass) HIPCHK(hipMalloc(&x->d_inv_mass, sizeof(double) * (size_t)x->cfg.dim));
+  // stream-ordered behind the launches that still read the previous vector; the host vector is a temporary or about to change: wait
+  HIPCHK(hipMemcpyAsync(x->d_inv_mass, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, x->stream));
+  HIPCHK(hipStreamSynchronize(x->stream));
+  return MFM_OK;
+}
+extern "C" int mfm_hmc_set_inverse_mass(mfm_ctx* x, const double* h_inv_mass, int32_t n) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  const int d = x->cfg.dim;
+  if (n == 0 && !h_inv_mass) {                       // back to unit mass and the unit instances
+    if (!x->h_inv_mass.empty() && x->d_inv_mass) { if (const int rc = inv_mass_upload(x, std::vector<double>((size_t)d, 1.0))) return rc; }
+    x->h_inv_mass.clear();
+    return MFM_OK;
+  }
+  if (n != d || !h_inv_mass) return fail(MFM_EINVAL, "inv_mass must hold dim = %d entries (got n = %d%s); n = 0 with a null pointer returns to unit mass", d, n, h_inv_mass ? "" : ", null pointer");
+  for (int j = 0; j < d; ++j)
+    if (!(std::isfinite(h_inv_mass[j]) && h_inv_mass[j] > 0)) return fail(MFM_EINVAL, "inv_mass[%d] = %g: every entry must be finite and positive", j, h_inv_mass[j]);
+  const std::vector<double> h(h_inv_mass, h_inv_mass + d);
+  if (const int rc = inv_mass_upload(x, h)) return rc;
+  x->h_inv_mass = h;
+  return MFM_OK;
+}
+extern "C" int mfm_hmc_get_inverse_mass(mfm_ctx* x, double* h_out, int32_t* h_is_set) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  const bool set = !x->h_inv_mass.empty();
+  if (h_out) for (int j = 0; j < x->cfg.dim; ++j) h_out[j] = set ? x->h_inv_mass[(size_t)j] : 1.0;
+  if (h_is_set) *h_is_set = set ? 1 : 0;
+  return MFM_OK;
 }
 
 static int hmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
@@ -766,22 +803,40 @@ static int warmup_check(mfm_ctx* x, int key_mode, const uint32_t* d_keys, double
   return MFM_OK;
 }
 
-extern "C" int mfm_hmc_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int32_t num_steps,
-                              int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
-                              double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
+// window: mfm_hmc_warmup_window, which always runs the mass instances (the context's vector, or ones) and takes the window's sums
+static int hmc_warmup_common(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int32_t num_steps,
+                             int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
+                             double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj, bool window, double* d_pos_sum,
+                             double* d_pos_sumsq) {
   if (const int rc = warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg)) return rc;
   if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
+  if (window && (!d_pos_sum || !d_pos_sumsq)) return fail(MFM_EINVAL, "d_pos_sum and d_pos_sumsq must not be null");
   if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  if (window && !x->d_inv_mass) { if (const int rc = inv_mass_upload(x, std::vector<double>((size_t)x->cfg.dim, 1.0))) return rc; }
   HmcRunArgs r; memset(&r, 0, sizeof r);
   r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, num_steps, d_pos, d_logp, d_grad, nullptr, nullptr);
+  if (window) r.h.minv = x->d_inv_mass;
   r.key_mode = key_mode; r.n_steps = n_steps;
   r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
-  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj};
+  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj, d_pos_sum, d_pos_sumsq};
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_warmup(r, w, x->stream)) return too_large(x, "HMC");
   LAUNCHCHK();
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
   return MFM_OK;
+}
+extern "C" int mfm_hmc_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int32_t num_steps,
+                              int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
+                              double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
+  return hmc_warmup_common(x, key_mode, k0, k1, d_keys, beta, step0, num_steps, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg, d_step_last,
+                           d_n_acc, d_acc_sum, d_step_traj, false, nullptr, nullptr);
+}
+extern "C" int mfm_hmc_warmup_window(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0,
+                                     int32_t num_steps, int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad,
+                                     double* d_step_avg, double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj,
+                                     double* d_pos_sum, double* d_pos_sumsq) { use_ctx(x);
+  return hmc_warmup_common(x, key_mode, k0, k1, d_keys, beta, step0, num_steps, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg, d_step_last,
+                           d_n_acc, d_acc_sum, d_step_traj, true, d_pos_sum, d_pos_sumsq);
 }
 
 extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int textbook,
@@ -799,7 +854,7 @@ extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k
   r.m.pos = d_pos; r.m.logp = d_logp; r.m.grad = d_grad;
   r.key_mode = key_mode; r.n_steps = n_steps;
   r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
-  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj};
+  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj, nullptr, nullptr};
   ProfScope ps_(x, PROF_MALA);
   if (launch_mala_warmup(r, w, x->stream)) return too_large(x, "MALA");
   LAUNCHCHK();

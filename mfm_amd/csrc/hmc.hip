@@ -7,6 +7,10 @@
 // the trajectory's position is rounded to float32 after every drift (it is what the target is evaluated at); energies are summed in
 // float64 over the wave.  Targets: phi-four and the Gaussian mixtures (row_value_grad); the Cox process needs the K^-1 GEMM tile
 // (lgcp.hip) and is not served.
+// With a diagonal inverse mass matrix minv (mfm_hmc_set_inverse_mass; blackjax's inverse_mass_matrix as a vector) the MASS instances run:
+// momentum p_j = n_j / sqrt(minv_j), H = -logp + sum_j minv_j p_j^2 / 2, drift x_j += eps minv_j p_j.  Every product with minv is written
+// so that minv == 1 gives the unit instances' bits (1 * p and n / 1 are exact); the unit instances are compiled from the lines they
+// always had.
 #pragma once
 // (included by api.hip after mala.hip: mcmc.hip.h, MalaArgs' helpers row_value_grad, MALA_DISPATCH, mala_smem)
 
@@ -19,6 +23,7 @@ struct HmcArgs {
   double beta, eps;
   float* pos; double* logp; float* grad;              // state, updated in place
   float* acc_prob; uint8_t* accepted;                 // info (may be null)
+  const double* minv;                                 // [d] diagonal of the inverse mass matrix: read by the MASS instances only
 };
 
 // the float64 draws and the acceptance exponential as a single-step launch makes them: in line (hmc_run.hip calls them out of line)
@@ -58,22 +63,34 @@ struct HmcInHbm {
 // 4.10 has the figures): the trajectory's x, g and momentum are this function's OWN arrays, not the caller's handed in by reference;
 // and the state is read into x0 / g0 and copied to x / g, as the step kernel always did.  xs: the wave's LDS row (pads written), gsm: the mixtures'
 // gradient scratch; both are left as the last row_value_grad read them (no trailing barrier).
-template <int MAXIT, bool BCRT, class State, class Draw>
+// MASS: minv[j] is the diagonal of the inverse mass matrix (see the head of this file).  It stays in registers through MAXIT 4 and is
+// read again from its d * 8 cache-resident bytes at every use above (DESIGN.md section 4.12 has the figures); !MASS never reads it.
+template <int MAXIT, bool BCRT, bool MASS, class State, class Draw>
 __device__ __forceinline__ void hmc_trajectory(const TargetDev& T, double beta, double eps, int num_steps, Key2 kb, int d, int lane,
-                                               float* xs, float* gsm, State& st, Draw dr) {
+                                               float* xs, float* gsm, const double* minv, State& st, Draw dr) {
 #pragma clang fp contract(off)
   const Key2 k_mom = mcmc_step_key(kb, MCMC_K_INT), k_acc = mcmc_step_key(kb, MCMC_K_RMH);
   float x0[MAXIT], g0[MAXIT], x[MAXIT], g[MAXIT];      // (x0 / g0: the state as it comes, see above)
   double p[MAXIT];
+  constexpr bool MREG = MASS && MAXIT <= 4;            // minv in registers
+  double mi[MREG ? MAXIT : 1];
   double kin = 0.0;
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
     const int j = lane + 64 * it;
     x0[it] = 0.f; g0[it] = 0.f; p[it] = 0.0;
+    if constexpr (MREG) mi[it] = 1.0;
     if (j < d) {
       st.element(it, j, x0[it], g0[it]);
+      if constexpr (MASS) {
+        const double m = minv[j];
+        if constexpr (MREG) mi[it] = m;
+        p[it] = dr.normal(k_mom, (uint32_t)j, (uint32_t)d) / sqrt(m);
+        kin += m * p[it] * p[it];
+      } else {
       p[it] = dr.normal(k_mom, (uint32_t)j, (uint32_t)d);
       kin += p[it] * p[it];
+      }
     }
     x[it] = x0[it]; g[it] = g0[it];
   }
@@ -86,6 +103,10 @@ __device__ __forceinline__ void hmc_trajectory(const TargetDev& T, double beta, 
       const int j = lane + 64 * it;
       if (j < d) {
         p[it] = p[it] + 0.5 * eps * (double)g[it];                       // half kick
+        if constexpr (MASS) {
+          const double m = MREG ? mi[MREG ? it : 0] : minv[j];
+          x[it] = (float)((double)x[it] + eps * (m * p[it]));            // drift
+        } else
         x[it] = (float)((double)x[it] + eps * p[it]);                    // drift
         xs[j] = x[it];
       }
@@ -102,6 +123,13 @@ __device__ __forceinline__ void hmc_trajectory(const TargetDev& T, double beta, 
     }
   }
   double kin1 = 0.0;
+  if constexpr (MASS) {
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      const int j = lane + 64 * it;
+      if (j < d) kin1 += (MREG ? mi[MREG ? it : 0] : minv[j]) * p[it] * p[it];
+    }
+  } else
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) kin1 += (lane + 64 * it < d) ? p[it] * p[it] : 0.0;
   const double h1 = -lp + 0.5 * wave_sum(kin1);
@@ -110,7 +138,7 @@ __device__ __forceinline__ void hmc_trajectory(const TargetDev& T, double beta, 
   st.template finish<MAXIT>(acc, pa, lp, x, g, d, lane);
 }
 
-template <int MAXIT, bool BCRT = false>      // BCRT: as mala.hip's row kernels
+template <int MAXIT, bool BCRT = false, bool MASS = false>      // BCRT: as mala.hip's row kernels; MASS: hmc_trajectory
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -122,7 +150,31 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
   const Key2 kb = mcmc_chain_key(a.key, a.keys, a.n_total, a.chain_offset, b);
   if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
   HmcInHbm st{a, (size_t)b * d, b};
-  hmc_trajectory<MAXIT, BCRT>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, st, HmcInline());
+  hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcInline());
 }
 
-int launch_hmc_step(const HmcArgs& a, hipStream_t stream) { MALA_DISPATCH(hmc_step_kernel, a); return 0; }
+// MALA_DISPATCH (mala.hip) onto the MASS instances of the three HMC kernels
+#define HMC_MASS_DISPATCH(KERN, ...)                                                                    \
+  do {                                                                                                  \
+    int nit = (a.T.dim + 63) / 64;                                                                      \
+    dim3 grid((a.B + MALA_WAVES - 1) / MALA_WAVES), block(MALA_WAVES * 64);                             \
+    size_t sm = mala_smem(a.T.dim);                                                                     \
+    if (a.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.T)) {                                         \
+      if (nit <= 1) hipLaunchKernelGGL((KERN<1, true, true>), grid, block, sm, stream, __VA_ARGS__);         \
+      else if (nit <= 4) hipLaunchKernelGGL((KERN<4, true, true>), grid, block, sm, stream, __VA_ARGS__);    \
+      else if (nit <= 16) hipLaunchKernelGGL((KERN<16, true, true>), grid, block, sm, stream, __VA_ARGS__);  \
+      else if (nit <= 32) hipLaunchKernelGGL((KERN<32, true, true>), grid, block, sm, stream, __VA_ARGS__);  \
+      else return -2;                                                                                   \
+    } else                                                                                              \
+    if (nit <= 1) hipLaunchKernelGGL((KERN<1, false, true>), grid, block, sm, stream, __VA_ARGS__);          \
+    else if (nit <= 4) hipLaunchKernelGGL((KERN<4, false, true>), grid, block, sm, stream, __VA_ARGS__);     \
+    else if (nit <= 16) hipLaunchKernelGGL((KERN<16, false, true>), grid, block, sm, stream, __VA_ARGS__);   \
+    else if (nit <= 32) hipLaunchKernelGGL((KERN<32, false, true>), grid, block, sm, stream, __VA_ARGS__);   \
+    else return -2;                                                                                     \
+  } while (0)
+
+// (a.minv non-null: the MASS instances)
+int launch_hmc_step(const HmcArgs& a, hipStream_t stream) {
+  if (a.minv) HMC_MASS_DISPATCH(hmc_step_kernel, a); else MALA_DISPATCH(hmc_step_kernel, a);
+  return 0;
+}

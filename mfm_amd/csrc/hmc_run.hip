@@ -47,7 +47,7 @@ template <int MAXIT> struct HmcResident {
   }
 };
 
-template <int MAXIT, bool BCRT = false>
+template <int MAXIT, bool BCRT = false, bool MASS = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_run_kernel(HmcRunArgs r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const HmcArgs& a = r.h;
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_run_kernel(HmcRunArgs r) 
   for (int s = 0; s < r.n_steps; ++s) {
     const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
     HmcResident<MAXIT> st{x, g, lp, false, 0.0};
-    hmc_trajectory<MAXIT, BCRT>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, st, HmcCalled());
+    hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcCalled());
     const bool acc = st.acc;
     const double p = st.pa;
     n_acc += acc ? 1 : 0;
@@ -116,6 +116,6 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_run_kernel(HmcRunArgs r) 
 
 int launch_hmc_run(const HmcRunArgs& r, hipStream_t stream) {
   const HmcArgs& a = r.h;
-  MALA_DISPATCH(hmc_run_kernel, r);
+  if (a.minv) HMC_MASS_DISPATCH(hmc_run_kernel, r); else MALA_DISPATCH(hmc_run_kernel, r);
   return 0;
 }

@@ -18,6 +18,8 @@ struct WarmupArgs {
   double* step_avg;        // [B] exp(xbar_n), the result
   double* step_last;       // [B] exp(x_n) (may be null)
   double* step_traj;       // [n_steps][B] the step size USED at each step (may be null)
+  double* pos_sum;         // [B][d] sum over the steps of the state after accept / reject, and
+  double* pos_sumsq;       // [B][d] of its square (mfm_hmc_warmup_window: both or neither; the MASS instances of hmc_warmup_kernel only)
 };
 
 __device__ __attribute__((noinline)) double run_log(double v) { return log(v); }
@@ -44,7 +46,11 @@ __device__ __forceinline__ double warmup_next(DualAvg& da, int m, double p, doub
   return wave_first(run_exp(da.x));
 }
 
-template <int MAXIT, bool BCRT = false>
+// MASS (the instances of mfm_hmc_set_inverse_mass and mfm_hmc_warmup_window): hmc_trajectory's, and the window's sums.  With w.pos_sum
+// the state after every step's accept / reject, the float32 position as a double (its square is exact), is added in step order to two
+// float64 sums per element, which a window of any length leaves behind in place of its trajectory.  Through MAXIT 4 the sums ride in
+// registers and are stored once; above, they are kept in their own elements of the output, which only this lane touches.
+template <int MAXIT, bool BCRT = false, bool MASS = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs r, WarmupArgs w) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const HmcArgs& a = r.h;
@@ -71,14 +77,34 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
   double acc_sum = 0.0;
   DualAvg da = warmup_begin(a.eps);
   double eps = a.eps;                                     // the first step runs at the caller's value itself
+  constexpr bool SREG = MASS && MAXIT <= 4;               // the window's sums in registers
+  double sx[SREG ? MAXIT : 1], sxx[SREG ? MAXIT : 1];
+  if constexpr (MASS) {
+#pragma unroll
+    for (int it = 0; it < MAXIT; ++it) {
+      const int j = lane + 64 * it;
+      if constexpr (SREG) { sx[it] = 0.0; sxx[it] = 0.0; }
+      else if (w.pos_sum && j < d) { w.pos_sum[row + j] = 0.0; w.pos_sumsq[row + j] = 0.0; }
+    }
+  }
 
   for (int s = 0; s < r.n_steps; ++s) {
     const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
     if (w.step_traj && lane == 0) w.step_traj[(size_t)s * B + (size_t)b] = eps;
     HmcResident<MAXIT> st{x, g, lp, false, 0.0};
-    hmc_trajectory<MAXIT, BCRT>(a.T, a.beta, eps, a.num_steps, kb, d, lane, xs, gsm, st, HmcCalled());
+    hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcCalled());
     warmup_tally(n_acc, acc_sum, st.acc, st.pa);
     eps = warmup_next(da, s + 1, st.pa, w.target);
+    if constexpr (MASS) {
+#pragma clang fp contract(off)
+#pragma unroll
+      for (int it = 0; it < MAXIT; ++it) {
+        const int j = lane + 64 * it;
+        const double v = (double)x[it];
+        if constexpr (SREG) { sx[it] = sx[it] + v; sxx[it] = sxx[it] + v * v; }
+        else if (w.pos_sum && j < d) { w.pos_sum[row + j] = w.pos_sum[row + j] + v; w.pos_sumsq[row + j] = w.pos_sumsq[row + j] + v * v; }
+      }
+    }
     // the next step's first drift overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -89,6 +115,15 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
   for (int it = 0; it < MAXIT; ++it) {
     const int j = lane + 64 * it;
     if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
+  }
+  if constexpr (SREG) {
+    if (w.pos_sum) {
+#pragma unroll
+      for (int it = 0; it < MAXIT; ++it) {
+        const int j = lane + 64 * it;
+        if (j < d) { w.pos_sum[row + j] = sx[it]; w.pos_sumsq[row + j] = sxx[it]; }
+      }
+    }
   }
   const double avg = run_exp(da.xbar);
   if (lane == 0) {
@@ -193,7 +228,7 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_warmup_kernel(MalaRunArg
 
 int launch_hmc_warmup(const HmcRunArgs& r, const WarmupArgs& w, hipStream_t stream) {
   const HmcArgs& a = r.h;
-  MALA_DISPATCH(hmc_warmup_kernel, r, w);
+  if (a.minv) HMC_MASS_DISPATCH(hmc_warmup_kernel, r, w); else MALA_DISPATCH(hmc_warmup_kernel, r, w);
   return 0;
 }
 int launch_mala_warmup(const MalaRunArgs& r, const WarmupArgs& w, hipStream_t stream) {

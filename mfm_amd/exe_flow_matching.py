@@ -363,7 +363,9 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
     if adapt_stats:
         logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']} (mean acceptance probability over the warmup= {adapt_stats['adapt_acceptance']})")
-        wandb.log(adapt_stats)
+        if "adapted_inverse_mass" in adapt_stats:
+            logger.info(f"Adapted inverse mass matrix (diagonal): min= {adapt_stats['adapted_inverse_mass_min']}, max= {adapt_stats['adapted_inverse_mass_max']}")
+        wandb.log({k: v for k, v in adapt_stats.items() if k != "adapted_inverse_mass"})
         train_start += time.time() - adapt_start                                            # (train_time stays the training's: the warmup has ended, its result is on the host)
     metrics = torch.zeros(learning_iter, 4, device=eng.dev, dtype=torch.float64)            # loss, acc mean, acc std, target loss
     betas, lrs = [], []
@@ -466,6 +468,8 @@ def check_adapt_args(args):
     n_steps = int(getattr(args, "adapt_steps", 0) or 0)
     if n_steps < 0:
         raise ValueError(f"--adapt_steps must not be negative (got {n_steps})")
+    if n_steps == 0 and getattr(args, "adapt_mass", False):
+        raise ValueError("--adapt_mass adapts the mass matrix during the --adapt_steps N warmup steps: give N > 0")
     if n_steps > 0 and args.mcmc_per_flow_steps < 0:
         raise ValueError("--adapt_steps has nothing to adapt with mcmc_per_flow_steps < 0: that run trains on exact samples and takes no MCMC step")
     if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") != "hmc":
@@ -481,12 +485,27 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     value (geometric mean over the chains of all ranks) for the rest of the run, ``--ess_steps`` included; ``pos0``, the chains the
     training starts from, is not moved.  Returns ``adapted_step_size`` and ``adapt_acceptance``, the mean acceptance probability over
     the warmup's steps and chains.  The key is a child of ``key_gen`` that nothing else draws (``split(key_gen, 4)[3]``: the final
-    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``, ``--ess_steps`` ``split(key_gen, 3)[2]``)."""
+    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``, ``--ess_steps`` ``split(key_gen, 3)[2]``).
+
+    ``--adapt_mass``: the N steps run ``window_adaptation`` (``bblackjax/adaptation/window_adaptation.py``) instead, on the same key and
+    copy: step size and a diagonal mass matrix together.  The inverse mass matrix is installed on the engine's context, where the
+    training loop's ``hmc_step`` calls find it, and kept as ``args.inverse_mass_matrix`` for ``--ess_steps``; besides the two figures
+    above (``adapt_acceptance``: of the last segment) the result carries ``adapted_inverse_mass`` (the vector) and its ``_min`` / ``_max``."""
     n_steps = check_adapt_args(args)
     if n_steps <= 0:
         return {}
     from .bblackjax.mcmc.hmc import hmc
     from .engine import global_mean_std
+    if getattr(args, "adapt_mass", False):
+        from .bblackjax.adaptation.window_adaptation import window_adaptation
+        algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))
+        wa = window_adaptation(dist.logprob, int(args.hmc_steps), args.step_size, float(getattr(args, "adapt_target", 0.8)))
+        _, params, info = wa.run(jr.split(key_gen, 4)[3], algo.init(pos0), n_steps)
+        minv = params["inverse_mass_matrix"]
+        args.step_size, args.inverse_mass_matrix = params["step_size"], minv
+        eng.ctx.set_inverse_mass(minv)
+        return dict(adapted_step_size=params["step_size"], adapt_acceptance=info.acceptance_rates[-1], adapted_inverse_mass=minv,
+                    adapted_inverse_mass_min=float(minv.min()), adapted_inverse_mass_max=float(minv.max()))
     algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))
     _, info = algo.step.warmup(jr.split(key_gen, 4)[3], algo.init(pos0), n_steps, float(getattr(args, "adapt_target", 0.8)))
     args.step_size = info.pooled_step_size
@@ -510,7 +529,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
     if use_hmc:
         from .bblackjax.mcmc.hmc import hmc
-        algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))
+        algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps), getattr(args, "inverse_mass_matrix", None))      # (--adapt_mass)
     else:
         from .bblackjax.mcmc.mala import mala
         algo = mala(dist.logprob, args.step_size)
