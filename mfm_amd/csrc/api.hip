@@ -546,6 +546,34 @@ static LgcpArgs lgcp_args(mfm_ctx* x, int mode, double beta, double eps) {      
 static void count_mala_steps(mfm_ctx* x, int64_t n) { x->ctr[CTR_MALA] += n; x->ctr[CTR_MALA_BYTES] += n * 4 * (5 * x->cfg.dim + 5); }   // n single chain steps
 static int too_large(mfm_ctx* x, const char* kernel) { return fail(MFM_ETOOLARGE, "dim %d too large for the %s kernel", x->cfg.dim, kernel); }
 
+// The argument checks the sampler entry points share; each calls them in its own order (the first error of a call with several is part of the ABI)
+#define CHECKED(call) do { if (const int rc_ = (call)) return rc_; } while (0)
+static int check_state(const float* d_pos, const double* d_logp, const float* d_grad, double step) {
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
+  return MFM_OK;
+}
+static int check_run_keys(int key_mode, const uint32_t* d_keys, int32_t n_steps) {
+  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
+  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
+  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
+  return MFM_OK;
+}
+static int check_thin(int32_t thin, int32_t n_steps, const float* d_traj_pos, const double* d_traj_logp) {
+  if (thin < 0) return fail(MFM_EINVAL, "thin must not be negative (got %d)", thin);
+  if (thin > 0 && n_steps % thin) return fail(MFM_EINVAL, "thin (%d) must divide n_steps (%d)", thin, n_steps);
+  if (thin > 0 && !d_traj_pos && !d_traj_logp) return fail(MFM_EINVAL, "thin > 0 needs d_traj_pos or d_traj_logp");
+  return MFM_OK;
+}
+// a run's or a warmup's MALA arguments: the chain's own keys in key_mode 1, state in place
+static MalaArgs mala_run_args(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int textbook,
+                              float* d_pos, double* d_logp, float* d_grad) {
+  MalaArgs a = mala_args(x, beta);
+  a.key = Key2{k0, k1}; a.keys = key_mode == 1 ? d_keys : nullptr; a.eps = step; a.textbook = textbook;
+  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad;
+  return a;
+}
+
 // LGCP dimensions beyond the fused tile kernel (d > 1024) go through the wide family's propose / K^-1 GEMM / accept split
 static int wide_mala_lgcp(mfm_ctx* x, const LgcpArgs& l) {
   if (!x->wide) return -3;
@@ -630,14 +658,9 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
                             int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum,
                             float* d_acc, uint8_t* d_isacc, float* d_prop, float* d_pw, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
   NEED_TARGET();
-  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
-  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
-  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
-  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
-  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
-  if (thin < 0) return fail(MFM_EINVAL, "thin must not be negative (got %d)", thin);
-  if (thin > 0 && n_steps % thin) return fail(MFM_EINVAL, "thin (%d) must divide n_steps (%d)", thin, n_steps);
-  if (thin > 0 && !d_traj_pos && !d_traj_logp) return fail(MFM_EINVAL, "thin > 0 needs d_traj_pos or d_traj_logp");
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
   const int B = x->cfg.n_chain_local, d = x->cfg.dim;
   if (x->net.T.kind == MFM_TARGET_LGCP) {
     // workspace: keys uint32 [B][2] | acc_prob float [B] | accepted uint8 [B]
@@ -678,12 +701,9 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
     return MFM_OK;
   }
   MalaRunArgs r; memset(&r, 0, sizeof r);
-  r.m = mala_args(x, beta);
-  r.m.key = Key2{k0, k1}; r.m.keys = key_mode == 1 ? d_keys : nullptr; r.m.eps = step; r.m.textbook = textbook;
-  r.m.pos = d_pos; r.m.logp = d_logp; r.m.grad = d_grad;
+  r.m = mala_run_args(x, key_mode, k0, k1, d_keys, beta, step, textbook, d_pos, d_logp, d_grad);
   r.m.acc_prob = d_acc; r.m.accepted = d_isacc; r.m.proposed = d_prop; r.m.prop_weight = d_pw;
-  r.key_mode = key_mode; r.n_steps = n_steps; r.thin = thin;
-  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum; r.traj_pos = d_traj_pos; r.traj_logp = d_traj_logp;
+  r.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
   ProfScope ps_(x, PROF_MALA);
   if (launch_mala_run(r, x->stream)) return too_large(x, "MALA");
   LAUNCHCHK();
@@ -693,8 +713,16 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
   return MFM_OK;
 }
 
+// the HMC entry points' own two checks (shared like the ones above)
+static int check_num_steps(int num_steps) {
+  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
+  return MFM_OK;
+}
+static int hmc_refuse_cox(mfm_ctx* x) {
+  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "the HMC step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)");
+  return MFM_OK;
+}
 // Build-side mode (hmc.hip; not on the reference's MFM path): one HMC step of every local chain, state updated in place like mfm_mala_step
-static const char* const kHmcNoCox = "the HMC step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)";
 static HmcArgs hmc_args(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
                         double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
   HmcArgs a; memset(&a, 0, sizeof a);
@@ -740,10 +768,9 @@ extern "C" int mfm_hmc_get_inverse_mass(mfm_ctx* x, double* h_out, int32_t* h_is
 static int hmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
                            double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
   NEED_TARGET();
-  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
-  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
-  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
-  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_num_steps(num_steps));
+  CHECKED(hmc_refuse_cox(x));
   const HmcArgs a = hmc_args(x, k0, k1, d_keys, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_step(a, x->stream)) return too_large(x, "HMC");
@@ -767,20 +794,14 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
                            int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum,
                            float* d_acc, uint8_t* d_isacc, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
   NEED_TARGET();
-  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
-  if (!(step > 0)) return fail(MFM_EINVAL, "step_size must be positive");
-  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
-  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
-  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
-  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
-  if (thin < 0) return fail(MFM_EINVAL, "thin must not be negative (got %d)", thin);
-  if (thin > 0 && n_steps % thin) return fail(MFM_EINVAL, "thin (%d) must divide n_steps (%d)", thin, n_steps);
-  if (thin > 0 && !d_traj_pos && !d_traj_logp) return fail(MFM_EINVAL, "thin > 0 needs d_traj_pos or d_traj_logp");
-  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_num_steps(num_steps));
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  CHECKED(hmc_refuse_cox(x));
   HmcRunArgs r; memset(&r, 0, sizeof r);
   r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
-  r.key_mode = key_mode; r.n_steps = n_steps; r.thin = thin;
-  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum; r.traj_pos = d_traj_pos; r.traj_logp = d_traj_logp;
+  r.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_run(r, x->stream)) return too_large(x, "HMC");
   LAUNCHCHK();
@@ -793,11 +814,8 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
 static int warmup_check(mfm_ctx* x, int key_mode, const uint32_t* d_keys, double step0, int32_t n_steps, double target_accept, const float* d_pos,
                         const double* d_logp, const float* d_grad, const double* d_step_avg) {
   NEED_TARGET();
-  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
-  if (!(step0 > 0)) return fail(MFM_EINVAL, "step_size must be positive");
-  if (key_mode != 0 && key_mode != 1) return fail(MFM_EINVAL, "key_mode must be 0 (step-major) or 1 (chain-major) (got %d)", key_mode);
-  if (key_mode == 1 && !d_keys) return fail(MFM_EINVAL, "key_mode 1 needs d_keys (one key per chain)");
-  if (n_steps < 1) return fail(MFM_EINVAL, "n_steps must be at least 1 (got %d)", n_steps);
+  CHECKED(check_state(d_pos, d_logp, d_grad, step0));
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
   if (!(target_accept > 0 && target_accept < 1)) return fail(MFM_EINVAL, "target_accept must lie strictly inside (0, 1) (got %g)", target_accept);
   if (!d_step_avg) return fail(MFM_EINVAL, "d_step_avg must not be null");
   return MFM_OK;
@@ -808,16 +826,15 @@ static int hmc_warmup_common(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1,
                              int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
                              double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj, bool window, double* d_pos_sum,
                              double* d_pos_sumsq) {
-  if (const int rc = warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg)) return rc;
-  if (num_steps < 1 || num_steps > 100000) return fail(MFM_EINVAL, "num_steps must be in [1, 100000] (got %d)", num_steps);
+  CHECKED(warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg));
+  CHECKED(check_num_steps(num_steps));
   if (window && (!d_pos_sum || !d_pos_sumsq)) return fail(MFM_EINVAL, "d_pos_sum and d_pos_sumsq must not be null");
-  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "%s", kHmcNoCox);
-  if (window && !x->d_inv_mass) { if (const int rc = inv_mass_upload(x, std::vector<double>((size_t)x->cfg.dim, 1.0))) return rc; }
+  CHECKED(hmc_refuse_cox(x));
+  if (window && !x->d_inv_mass) CHECKED(inv_mass_upload(x, std::vector<double>((size_t)x->cfg.dim, 1.0)));
   HmcRunArgs r; memset(&r, 0, sizeof r);
   r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, num_steps, d_pos, d_logp, d_grad, nullptr, nullptr);
   if (window) r.h.minv = x->d_inv_mass;
-  r.key_mode = key_mode; r.n_steps = n_steps;
-  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
+  r.t = RunTail{key_mode, n_steps, 0, d_n_acc, d_acc_sum, nullptr, nullptr};      // (a warmup keeps no trajectory)
   const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj, d_pos_sum, d_pos_sumsq};
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_warmup(r, w, x->stream)) return too_large(x, "HMC");
@@ -842,18 +859,15 @@ extern "C" int mfm_hmc_warmup_window(mfm_ctx* x, int key_mode, uint32_t k0, uint
 extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int textbook,
                                int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
                                double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
-  if (const int rc = warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg)) return rc;
+  CHECKED(warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg));
   if (x->net.T.kind == MFM_TARGET_LGCP)
     return fail(MFM_EUNSUPPORTED, "the step-size warmup serves the phi-four and mixture targets (the Cox process's run is a sequence of tile launches with a by-value step size)");
   if (!textbook)
     return fail(MFM_EINVAL, "the step-size warmup needs textbook = 1 (the as-written rule accepts with min(1, 1 / alpha): its acceptance does not fall as the step grows)");
   const int B = x->cfg.n_chain_local, d = x->cfg.dim;
   MalaRunArgs r; memset(&r, 0, sizeof r);
-  r.m = mala_args(x, beta);
-  r.m.key = Key2{k0, k1}; r.m.keys = key_mode == 1 ? d_keys : nullptr; r.m.eps = step0; r.m.textbook = textbook;
-  r.m.pos = d_pos; r.m.logp = d_logp; r.m.grad = d_grad;
-  r.key_mode = key_mode; r.n_steps = n_steps;
-  r.n_acc = d_n_acc; r.acc_sum = d_acc_sum;
+  r.m = mala_run_args(x, key_mode, k0, k1, d_keys, beta, step0, textbook, d_pos, d_logp, d_grad);
+  r.t = RunTail{key_mode, n_steps, 0, d_n_acc, d_acc_sum, nullptr, nullptr};      // (a warmup keeps no trajectory)
   const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj, nullptr, nullptr};
   ProfScope ps_(x, PROF_MALA);
   if (launch_mala_warmup(r, w, x->stream)) return too_large(x, "MALA");

@@ -12,7 +12,7 @@
 // so that minv == 1 gives the unit instances' bits (1 * p and n / 1 are exact); the unit instances are compiled from the lines they
 // always had.
 #pragma once
-// (included by api.hip after mala.hip: mcmc.hip.h, MalaArgs' helpers row_value_grad, MALA_DISPATCH, mala_smem)
+// (included by api.hip after mala.hip: mcmc.hip.h, MalaArgs' helpers row_value_grad, ROW_DISPATCH / MALA_DISPATCH, mala_smem)
 
 struct HmcArgs {
   TargetDev T;
@@ -153,25 +153,9 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_step_kernel(HmcArgs a) {
   hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcInline());
 }
 
-// MALA_DISPATCH (mala.hip) onto the MASS instances of the three HMC kernels
-#define HMC_MASS_DISPATCH(KERN, ...)                                                                    \
-  do {                                                                                                  \
-    int nit = (a.T.dim + 63) / 64;                                                                      \
-    dim3 grid((a.B + MALA_WAVES - 1) / MALA_WAVES), block(MALA_WAVES * 64);                             \
-    size_t sm = mala_smem(a.T.dim);                                                                     \
-    if (a.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.T)) {                                         \
-      if (nit <= 1) hipLaunchKernelGGL((KERN<1, true, true>), grid, block, sm, stream, __VA_ARGS__);         \
-      else if (nit <= 4) hipLaunchKernelGGL((KERN<4, true, true>), grid, block, sm, stream, __VA_ARGS__);    \
-      else if (nit <= 16) hipLaunchKernelGGL((KERN<16, true, true>), grid, block, sm, stream, __VA_ARGS__);  \
-      else if (nit <= 32) hipLaunchKernelGGL((KERN<32, true, true>), grid, block, sm, stream, __VA_ARGS__);  \
-      else return -2;                                                                                   \
-    } else                                                                                              \
-    if (nit <= 1) hipLaunchKernelGGL((KERN<1, false, true>), grid, block, sm, stream, __VA_ARGS__);          \
-    else if (nit <= 4) hipLaunchKernelGGL((KERN<4, false, true>), grid, block, sm, stream, __VA_ARGS__);     \
-    else if (nit <= 16) hipLaunchKernelGGL((KERN<16, false, true>), grid, block, sm, stream, __VA_ARGS__);   \
-    else if (nit <= 32) hipLaunchKernelGGL((KERN<32, false, true>), grid, block, sm, stream, __VA_ARGS__);   \
-    else return -2;                                                                                     \
-  } while (0)
+// ROW_DISPATCH (mala.hip) onto the MASS instances of the three HMC kernels
+#define HMC_MASS() , true
+#define HMC_MASS_DISPATCH(KERN, ...) ROW_DISPATCH(KERN, HMC_MASS, __VA_ARGS__)
 
 // (a.minv non-null: the MASS instances)
 int launch_hmc_step(const HmcArgs& a, hipStream_t stream) {

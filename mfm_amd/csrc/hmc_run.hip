@@ -10,16 +10,12 @@
 //
 // Keys (mcmc_run_key), as mala_run.hip.  key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_hmc_step uses its key.
 // key_mode 1 (chain-major): keys[b] is the chain's own key and step j uses split(keys[b], n_steps)[j].
-// (Included by api.hip after hmc.hip and mala_run.hip: HmcArgs, hmc_trajectory, run_normal64 / run_uniform01 / run_exp.)
+// (Included by api.hip after hmc.hip and mala_run.hip: HmcArgs, hmc_trajectory, run_normal64 / run_uniform01 / run_exp, and
+// resident.hip.h's mapping, key schedule, trajectory store and closing fence.)
 
 struct HmcRunArgs {
   HmcArgs h;               // target, keys, beta, eps, leapfrog steps, state (in place), the LAST step's info (may be null)
-  int key_mode;
-  int n_steps, thin;       // thin >= 1: the state after step j is kept when (j + 1) % thin == 0; 0: no trajectory
-  int32_t* n_acc;          // [B] accepted steps (may be null)
-  double* acc_sum;         // [B] sum of the acceptance probabilities (may be null)
-  float* traj_pos;         // [n_steps / thin][B][d] (may be null)
-  double* traj_logp;       // [n_steps / thin][B] (may be null)
+  RunTail t;
 };
 
 // the draws and the exponential through mala_run.hip's out-of-line wrappers (the reason is stated there): same instructions, same bits
@@ -51,16 +47,12 @@ template <int MAXIT, bool BCRT = false, bool MASS = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_run_kernel(HmcRunArgs r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const HmcArgs& a = r.h;
-  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rowlen = d + 2;
-  const int b = blockIdx.x * MALA_WAVES + wave;
-  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
-  float* const xs = smem + wave * rowlen + 1;
-  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
-  const size_t row = (size_t)b * d;
-  const size_t B = (size_t)a.B;
+  const int d = a.T.dim, lane = threadIdx.x & 63, b = resident_chain_index();      // (own scalars: resident.hip.h says why)
+  if (b >= a.B) return;
+  const ResidentChain c(smem, d, a.B, lane, b);
+  float* const xs = c.xs; float* const gsm = c.gsm; const size_t row = c.row;
 
-  float x[MAXIT], g[MAXIT];
+  float x[MAXIT], g[MAXIT];                               // (in line here: through resident_load the MAXIT 16 / 32 instances gain spill instructions, resident.hip.h)
   double lp = a.logp[b];
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
@@ -68,47 +60,34 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_run_kernel(HmcRunArgs r) 
     x[it] = 0.f; g[it] = 0.f;
     if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
   }
-  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
-  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  c.pads();
+  const Key2 kc = run_chain_key(c, a, r.t);
   int n_acc = 0;
   double acc_sum = 0.0, p_last = 0.0;
   bool acc_last = false;
 
-  for (int s = 0; s < r.n_steps; ++s) {
-    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
+  for (int s = 0; s < r.t.n_steps; ++s) {
+    const Key2 kb = run_step_key(c, a, r.t, kc, s);
     HmcResident<MAXIT> st{x, g, lp, false, 0.0};
     hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, a.eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcCalled());
     const bool acc = st.acc;
     const double p = st.pa;
     n_acc += acc ? 1 : 0;
     acc_sum += p;
-    if (s == r.n_steps - 1) { p_last = p; acc_last = acc; }
-    if (r.thin > 0 && (s + 1) % r.thin == 0) {
-      const size_t snap = (size_t)((s + 1) / r.thin - 1);
-      if (r.traj_pos) {
-#pragma unroll
-        for (int it = 0; it < MAXIT; ++it) {
-          const int j = lane + 64 * it;
-          if (j < d) r.traj_pos[(snap * B + (size_t)b) * (size_t)d + j] = x[it];
-        }
-      }
-      if (r.traj_logp && lane == 0) r.traj_logp[snap * B + (size_t)b] = lp;
-    }
-    // the next step's first drift overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (s == r.t.n_steps - 1) { p_last = p; acc_last = acc; }
+    resident_snapshot(c, r.t, s, x, lp);
+    resident_step_end();
   }
 
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
+  for (int it = 0; it < MAXIT; ++it) {                    // (the final store stays in line: resident.hip.h)
     const int j = lane + 64 * it;
     if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
   }
   if (lane == 0) {
     a.logp[b] = lp;
-    if (r.n_acc) r.n_acc[b] = n_acc;
-    if (r.acc_sum) r.acc_sum[b] = acc_sum;
+    if (r.t.n_acc) r.t.n_acc[b] = n_acc;
+    if (r.t.acc_sum) r.t.acc_sum[b] = acc_sum;
     if (a.acc_prob) a.acc_prob[b] = (float)p_last;
     if (a.accepted) a.accepted[b] = acc_last ? 1 : 0;
   }

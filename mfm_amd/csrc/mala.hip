@@ -255,24 +255,28 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_step_kernel(MalaArgs a) 
 // ---- launchers (called from the C ABI in api.hip) ---------------------------------------------------------
 static inline size_t mala_smem(int d) { return (size_t)(MALA_WAVES * (d + 2) + MALA_WAVES * MALA_MAXD_SMALL) * sizeof(float); }
 
-#define MALA_DISPATCH(KERN, ...)                                                             \
+// The one dispatch of every row kernel (`a`: its MalaArgs / HmcArgs, `stream`; returns -2 from the launcher past 32 elements per lane):
+// the instance KERN<MAXIT, BCRT MORE()> for the dimension and the phi-four boundary.  MORE names a macro that gives the template
+// arguments after BCRT: ROW_NO_MORE for none (KERN<1, false> is KERN<1>), HMC_MASS (hmc.hip) for the mass instances.
+#define ROW_NO_MORE()
+#define ROW_LAUNCH_(KERN, MAXIT, MORE, ...)                                                                    \
+  do {                                                                                                         \
+    if (bcrt) hipLaunchKernelGGL((KERN<MAXIT, true MORE()>), grid, block, sm, stream, __VA_ARGS__);            \
+    else hipLaunchKernelGGL((KERN<MAXIT, false MORE()>), grid, block, sm, stream, __VA_ARGS__);                \
+  } while (0)
+#define ROW_DISPATCH(KERN, MORE, ...)                                                        \
   do {                                                                                       \
-    int nit = (a.T.dim + 63) / 64;                                                           \
-    dim3 grid((a.B + MALA_WAVES - 1) / MALA_WAVES), block(MALA_WAVES * 64);                  \
-    size_t sm = mala_smem(a.T.dim);                                                          \
-    if (a.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.T)) {                              \
-      if (nit <= 1) hipLaunchKernelGGL((KERN<1, true>), grid, block, sm, stream, __VA_ARGS__);        \
-      else if (nit <= 4) hipLaunchKernelGGL((KERN<4, true>), grid, block, sm, stream, __VA_ARGS__);   \
-      else if (nit <= 16) hipLaunchKernelGGL((KERN<16, true>), grid, block, sm, stream, __VA_ARGS__); \
-      else if (nit <= 32) hipLaunchKernelGGL((KERN<32, true>), grid, block, sm, stream, __VA_ARGS__); \
-      else return -2;                                                                        \
-    } else                                                                                   \
-    if (nit <= 1) hipLaunchKernelGGL(KERN<1>, grid, block, sm, stream, __VA_ARGS__);         \
-    else if (nit <= 4) hipLaunchKernelGGL(KERN<4>, grid, block, sm, stream, __VA_ARGS__);    \
-    else if (nit <= 16) hipLaunchKernelGGL(KERN<16>, grid, block, sm, stream, __VA_ARGS__);  \
-    else if (nit <= 32) hipLaunchKernelGGL(KERN<32>, grid, block, sm, stream, __VA_ARGS__);  \
+    const int nit = (a.T.dim + 63) / 64;                                                     \
+    const dim3 grid((a.B + MALA_WAVES - 1) / MALA_WAVES), block(MALA_WAVES * 64);            \
+    const size_t sm = mala_smem(a.T.dim);                                                    \
+    const bool bcrt = a.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(a.T);                  \
+    if (nit <= 1) ROW_LAUNCH_(KERN, 1, MORE, __VA_ARGS__);                                   \
+    else if (nit <= 4) ROW_LAUNCH_(KERN, 4, MORE, __VA_ARGS__);                              \
+    else if (nit <= 16) ROW_LAUNCH_(KERN, 16, MORE, __VA_ARGS__);                            \
+    else if (nit <= 32) ROW_LAUNCH_(KERN, 32, MORE, __VA_ARGS__);                            \
     else return -2;                                                                          \
   } while (0)
+#define MALA_DISPATCH(KERN, ...) ROW_DISPATCH(KERN, ROW_NO_MORE, __VA_ARGS__)
 
 int launch_mala_init(const MalaArgs& a, hipStream_t stream) { MALA_DISPATCH(mala_init_kernel, a); return 0; }
 int launch_mala_step(const MalaArgs& a, hipStream_t stream) { MALA_DISPATCH(mala_step_kernel, a); return 0; }

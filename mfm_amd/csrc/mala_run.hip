@@ -10,16 +10,15 @@
 //
 // Keys (mcmc_run_key).  key_mode 0 (step-major): step j uses split(key, n_steps)[j] as mfm_mala_step uses its key.  key_mode 1
 // (chain-major): keys[b] is the chain's own key and step j uses split(keys[b], n_steps)[j].  Draws are always made in line.
+// The mapping, the key schedule, the thinned trajectory store and the step's closing fence are resident.hip.h's, shared with
+// hmc_run.hip and warmup.hip; a step is mala_resident_step below, which mala_warmup_kernel (warmup.hip) calls with eps per step.
 // (Included by api.hip after mala.hip: MalaArgs, row_value_grad, MALA_DISPATCH.)
+
+#include "resident.hip.h"
 
 struct MalaRunArgs {
   MalaArgs m;              // target, keys, beta, eps, textbook, state (in place), the LAST step's info (may be null); pre_n / pre_u unused
-  int key_mode;
-  int n_steps, thin;       // thin >= 1: the state after step j is kept when (j + 1) % thin == 0; 0: no trajectory
-  int32_t* n_acc;          // [B] accepted steps (may be null)
-  double* acc_sum;         // [B] sum of the acceptance probabilities (may be null)
-  float* traj_pos;         // [n_steps / thin][B][d] (may be null)
-  double* traj_logp;       // [n_steps / thin][B] (may be null)
+  RunTail t;
 };
 
 // The float64 draws and the acceptance exponential are CALLED, not inlined.  Their double-precision polynomial coefficients cannot be
@@ -31,97 +30,105 @@ __device__ __attribute__((noinline)) double run_uniform01(Key2 key) { return uni
 __device__ __attribute__((noinline)) double run_exp(double v) { return exp(v); }
 struct RunExp { __device__ __forceinline__ double operator()(double v) const { return run_exp(v); } };
 
+// The resident chain's registers and a step's outcome, as mala_resident_step sees them (HmcResident's counterpart, hmc_run.hip)
+template <int MAXIT> struct MalaResident {
+  float (&x)[MAXIT]; float (&g)[MAXIT]; double& lp;      // the chain: an accepted proposal is taken by select
+  float (&xn)[MAXIT];                                    // the last proposal (MalaArgs::proposed)
+  bool acc; double p;                                    // the step's outcome: accepted, the acceptance probability,
+  double lpn, th2;                                       // the proposal's log-density in this lane and the reduced back term (mala_prop_weight)
+  __device__ __forceinline__ void element(int it, float& xo, float& go) const { xo = x[it]; go = g[it]; }
+  __device__ __forceinline__ double logdensity() const { return lp; }
+  template <int M> __device__ __forceinline__ void finish(bool acc_, double p_, double lpn_, double th2_, const float (&xe)[M], const float (&ge)[M]) {
+    const double lpn0 = __shfl(lpn_, 0, 64);    // the value a single-step launch stores (lane 0's) and the next one loads in every lane
+#pragma unroll
+    for (int it = 0; it < M; ++it) {
+      x[it] = acc_ ? xe[it] : x[it];
+      g[it] = acc_ ? ge[it] : g[it];
+      xn[it] = xe[it];
+    }
+    lp = acc_ ? lpn0 : lp;
+    acc = acc_; p = p_; lpn = lpn_; th2 = th2_;
+  }
+};
+
+// ONE MALA step of the resident chain, with the step's chain key kb: every step of mala_run_kernel and of mala_warmup_kernel
+// (warmup.hip).  mala_chain_step's arithmetic through mcmc.hip.h, in the strict form (same draws, same reductions).  eps and
+// s2e = mala_s2e(eps) are the caller's: loop-invariant in the run, this wave's own per step in the warmup.  The shape is
+// hmc_trajectory's (hmc.hip, DESIGN.md sections 4.8 / 4.10): the state comes through `st` into this function's OWN arrays and the
+// outcome goes back through st.finish -- with the kernel's arrays handed in by reference the large instances lose a wave or spill.
+// xs: the wave's LDS row (pads written), gsm: the mixtures' gradient scratch; the caller ends the step with resident_step_end.
+template <int MAXIT, bool BCRT, class State>
+__device__ __forceinline__ void mala_resident_step(const TargetDev& T, double beta, double eps, double s2e, int textbook, Key2 kb, int d, int lane,
+                                                   float* xs, float* gsm, State& st) {
+  const Key2 k_int = mcmc_step_key(kb, MCMC_K_INT), k_rmh = mcmc_step_key(kb, MCMC_K_RMH);
+  float x[MAXIT], g[MAXIT], xn[MAXIT], gn[MAXIT];
+  double th1 = 0.0;                       // |x' - x - eps g|^2 = 2 eps |noise|^2
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    st.element(it, x[it], g[it]);
+    xn[it] = 0.f; gn[it] = 0.f;
+    if (j < d) {
+      const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);
+      xn[it] = mala_propose<false>(x[it], g[it], n, eps, s2e, th1);
+      xs[j] = xn[it];
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the stencil reads its neighbours' proposal elements from this wave's row
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const double lpn = row_value_grad<MAXIT, BCRT>(T, beta, xs, d, lane, gn, gsm);
+  double th2 = 0.0;                       // |x - x' - eps g'|^2
+#pragma unroll
+  for (int it = 0; it < MAXIT; ++it) {
+    const int j = lane + 64 * it;
+    if (j < d) mala_back<false>(x[it], xn[it], gn[it], eps, th2);
+  }
+  th1 = wave_sum(th1); th2 = wave_sum(th2);
+  const double p = mala_accept_p<false>(st.logdensity(), lpn, th1, th2, eps, textbook, RunExp());
+  const double u = run_uniform01(k_rmh);
+  st.template finish<MAXIT>(u < p, p, lpn, th2, xn, gn);
+}
+
 template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const MalaArgs& a = r.m;
-  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rowlen = d + 2;
-  const int b = blockIdx.x * MALA_WAVES + wave;
-  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
-  float* const xs = smem + wave * rowlen + 1;
-  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
-  const size_t row = (size_t)b * d;
-  const size_t B = (size_t)a.B;
+  const int d = a.T.dim, lane = threadIdx.x & 63, b = resident_chain_index();      // (own scalars: resident.hip.h says why)
+  if (b >= a.B) return;
+  const ResidentChain c(smem, d, a.B, lane, b);
+  float* const xs = c.xs; float* const gsm = c.gsm; const size_t row = c.row;
 
-  float x[MAXIT], g[MAXIT], xn[MAXIT];
-  double lp = a.logp[b];
+  ResidentState<MAXIT> cs = resident_load<MAXIT>(c, a);
+  float (&x)[MAXIT] = cs.x; float (&g)[MAXIT] = cs.g; double& lp = cs.lp;
+  c.pads();
+  float xn[MAXIT];
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int j = lane + 64 * it;
-    x[it] = 0.f; g[it] = 0.f; xn[it] = 0.f;
-    if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
-  }
-  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
-  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  for (int it = 0; it < MAXIT; ++it) xn[it] = 0.f;
+  const Key2 kc = run_chain_key(c, a, r.t);
   const double s2e = mala_s2e(a.eps);
   int n_acc = 0;
   double acc_sum = 0.0, p_last = 0.0, pw_last = 0.0;
   bool acc_last = false;
 
-  for (int s = 0; s < r.n_steps; ++s) {
-    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
-    const Key2 k_int = mcmc_step_key(kb, MCMC_K_INT), k_rmh = mcmc_step_key(kb, MCMC_K_RMH);
-    double th1 = 0.0;                       // |x' - x - eps g|^2 = 2 eps |noise|^2
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int j = lane + 64 * it;
-      if (j < d) {
-        const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);
-        xn[it] = mala_propose<false>(x[it], g[it], n, a.eps, s2e, th1);
-        xs[j] = xn[it];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the stencil reads its neighbours' proposal elements from this wave's row
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-    float gn[MAXIT];
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) gn[it] = 0.f;
-    const double lpn = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, gn, gsm);
-    double th2 = 0.0;                       // |x - x' - eps g'|^2
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int j = lane + 64 * it;
-      if (j < d) mala_back<false>(x[it], xn[it], gn[it], a.eps, th2);
-    }
-    th1 = wave_sum(th1); th2 = wave_sum(th2);
-    const double p = mala_accept_p<false>(lp, lpn, th1, th2, a.eps, a.textbook, RunExp());
-    const double u = run_uniform01(k_rmh);
-    const bool acc = u < p;
-    const double lpn0 = __shfl(lpn, 0, 64);     // the value a single-step launch stores (lane 0's) and the next one loads in every lane
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      x[it] = acc ? xn[it] : x[it];
-      g[it] = acc ? gn[it] : g[it];
-    }
-    lp = acc ? lpn0 : lp;
+  for (int s = 0; s < r.t.n_steps; ++s) {
+    const Key2 kb = run_step_key(c, a, r.t, kc, s);
+    MalaResident<MAXIT> st{x, g, lp, xn, false, 0.0, 0.0, 0.0};
+    mala_resident_step<MAXIT, BCRT>(a.T, a.beta, a.eps, s2e, a.textbook, kb, d, lane, xs, gsm, st);
+    const bool acc = st.acc;
+    const double p = st.p;
     n_acc += acc ? 1 : 0;
     acc_sum += p;
-    if (s == r.n_steps - 1) {
+    if (s == r.t.n_steps - 1) {
       p_last = p; acc_last = acc;
-      if (a.prop_weight) pw_last = mala_prop_weight(lpn, th2, a.eps, RunExp());
+      if (a.prop_weight) pw_last = mala_prop_weight(st.lpn, st.th2, a.eps, RunExp());
     }
-    if (r.thin > 0 && (s + 1) % r.thin == 0) {
-      const size_t snap = (size_t)((s + 1) / r.thin - 1);
-      if (r.traj_pos) {
-#pragma unroll
-        for (int it = 0; it < MAXIT; ++it) {
-          const int j = lane + 64 * it;
-          if (j < d) r.traj_pos[(snap * B + (size_t)b) * (size_t)d + j] = x[it];
-        }
-      }
-      if (r.traj_logp && lane == 0) r.traj_logp[snap * B + (size_t)b] = lp;
-    }
-    // the next step overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    resident_snapshot(c, r.t, s, x, lp);
+    resident_step_end();
   }
 
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
+  for (int it = 0; it < MAXIT; ++it) {                    // (the final store stays in line: resident.hip.h)
     const int j = lane + 64 * it;
     if (j < d) {
       a.pos[row + j] = x[it]; a.grad[row + j] = g[it];
@@ -130,8 +137,8 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void mala_run_kernel(MalaRunArgs r
   }
   if (lane == 0) {
     a.logp[b] = lp;
-    if (r.n_acc) r.n_acc[b] = n_acc;
-    if (r.acc_sum) r.acc_sum[b] = acc_sum;
+    if (r.t.n_acc) r.t.n_acc[b] = n_acc;
+    if (r.t.acc_sum) r.t.acc_sum[b] = acc_sum;
     if (a.acc_prob) a.acc_prob[b] = (float)p_last;
     if (a.accepted) a.accepted[b] = acc_last ? 1 : 0;
     if (a.prop_weight) a.prop_weight[b] = (float)pw_last;

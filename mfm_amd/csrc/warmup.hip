@@ -1,7 +1,8 @@
 // Step-size warmup: n_steps HMC or MALA steps of every chain in ONE launch, in which every chain adapts its OWN step size by dual
 // averaging towards a target acceptance probability (mfm_hmc_warmup / mfm_mala_warmup; the recursion: include/mfm.h, DualAvg in mcmc.hip.h).
 //
-// hmc_warmup_kernel / mala_warmup_kernel are hmc_run_kernel / mala_run_kernel (mapping, residency, key schedule, instances) without the
+// hmc_warmup_kernel / mala_warmup_kernel are hmc_run_kernel / mala_run_kernel (the mapping, key schedule and closing fence of
+// resident.hip.h; the same residency and instances) without the
 // trajectory and the last step's info, and with this wave's step size eps_m in place of the launch's: step m of chain b gives the bits
 // of a single-step launch (mfm_hmc_step_keys; mfm_mala_step_keys with textbook = 1) with the scalar step size eps_m[b] and the same step
 // key (tests/test_gpu_warmup.py).  Every HMC chain makes the same number of leapfrog steps, so different step sizes cost no divergence.
@@ -46,6 +47,18 @@ __device__ __forceinline__ double warmup_next(DualAvg& da, int m, double p, doub
   return wave_first(run_exp(da.x));
 }
 
+// both kernels' epilogue, after the state's final store: the log-density, the averaged step size, the last one, the two tallies
+__device__ __forceinline__ void warmup_finish(const ResidentChain& c, const RunTail& t, const WarmupArgs& w, const DualAvg& da, double eps, int n_acc, double acc_sum, double* logp, double lp) {
+  const double avg = run_exp(da.xbar);
+  if (c.lane == 0) {
+    logp[c.b] = lp;
+    w.step_avg[c.b] = avg;
+    if (w.step_last) w.step_last[c.b] = eps;
+    if (t.n_acc) t.n_acc[c.b] = n_acc;
+    if (t.acc_sum) t.acc_sum[c.b] = acc_sum;
+  }
+}
+
 // MASS (the instances of mfm_hmc_set_inverse_mass and mfm_hmc_warmup_window): hmc_trajectory's, and the window's sums.  With w.pos_sum
 // the state after every step's accept / reject, the float32 position as a double (its square is exact), is added in step order to two
 // float64 sums per element, which a window of any length leaves behind in place of its trajectory.  Through MAXIT 4 the sums ride in
@@ -54,16 +67,12 @@ template <int MAXIT, bool BCRT = false, bool MASS = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs r, WarmupArgs w) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const HmcArgs& a = r.h;
-  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rowlen = d + 2;
-  const int b = blockIdx.x * MALA_WAVES + wave;
-  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
-  float* const xs = smem + wave * rowlen + 1;
-  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
-  const size_t row = (size_t)b * d;
-  const size_t B = (size_t)a.B;
+  const int d = a.T.dim, lane = threadIdx.x & 63, b = resident_chain_index();      // (own scalars: resident.hip.h says why)
+  if (b >= a.B) return;
+  const ResidentChain c(smem, d, a.B, lane, b);
+  float* const xs = c.xs; float* const gsm = c.gsm; const size_t row = c.row, B = c.B;
 
-  float x[MAXIT], g[MAXIT];
+  float x[MAXIT], g[MAXIT];                               // (in line here: through resident_load the MAXIT 16 / 32 instances gain spill instructions, resident.hip.h)
   double lp = a.logp[b];
 #pragma unroll
   for (int it = 0; it < MAXIT; ++it) {
@@ -71,8 +80,8 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
     x[it] = 0.f; g[it] = 0.f;
     if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
   }
-  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
-  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  c.pads();
+  const Key2 kc = run_chain_key(c, a, r.t);
   int n_acc = 0;
   double acc_sum = 0.0;
   DualAvg da = warmup_begin(a.eps);
@@ -88,8 +97,8 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
     }
   }
 
-  for (int s = 0; s < r.n_steps; ++s) {
-    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
+  for (int s = 0; s < r.t.n_steps; ++s) {
+    const Key2 kb = run_step_key(c, a, r.t, kc, s);
     if (w.step_traj && lane == 0) w.step_traj[(size_t)s * B + (size_t)b] = eps;
     HmcResident<MAXIT> st{x, g, lp, false, 0.0};
     hmc_trajectory<MAXIT, BCRT, MASS>(a.T, a.beta, eps, a.num_steps, kb, d, lane, xs, gsm, a.minv, st, HmcCalled());
@@ -105,14 +114,11 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
         else if (w.pos_sum && j < d) { w.pos_sum[row + j] = w.pos_sum[row + j] + v; w.pos_sumsq[row + j] = w.pos_sumsq[row + j] + v * v; }
       }
     }
-    // the next step's first drift overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    resident_step_end();
   }
 
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
+  for (int it = 0; it < MAXIT; ++it) {                    // (the final store stays in line: resident.hip.h)
     const int j = lane + 64 * it;
     if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
   }
@@ -125,105 +131,48 @@ __global__ __launch_bounds__(MALA_WAVES * 64) void hmc_warmup_kernel(HmcRunArgs 
       }
     }
   }
-  const double avg = run_exp(da.xbar);
-  if (lane == 0) {
-    a.logp[b] = lp;
-    w.step_avg[b] = avg;
-    if (w.step_last) w.step_last[b] = eps;
-    if (r.n_acc) r.n_acc[b] = n_acc;
-    if (r.acc_sum) r.acc_sum[b] = acc_sum;
-  }
+  warmup_finish(c, r.t, w, da, eps, n_acc, acc_sum, a.logp, lp);
 }
 
 template <int MAXIT, bool BCRT = false>
 __global__ __launch_bounds__(MALA_WAVES * 64) void mala_warmup_kernel(MalaRunArgs r, WarmupArgs w) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const MalaArgs& a = r.m;
-  const int d = a.T.dim, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int rowlen = d + 2;
-  const int b = blockIdx.x * MALA_WAVES + wave;
-  if (b >= a.B) return;                                   // (wave-uniform; no workgroup barrier below)
-  float* const xs = smem + wave * rowlen + 1;
-  float* const gsm = smem + MALA_WAVES * rowlen + wave * MALA_MAXD_SMALL;
-  const size_t row = (size_t)b * d;
-  const size_t B = (size_t)a.B;
+  const int d = a.T.dim, lane = threadIdx.x & 63, b = resident_chain_index();      // (own scalars: resident.hip.h says why)
+  if (b >= a.B) return;
+  const ResidentChain c(smem, d, a.B, lane, b);
+  float* const xs = c.xs; float* const gsm = c.gsm; const size_t row = c.row, B = c.B;
 
-  float x[MAXIT], g[MAXIT], xn[MAXIT];
-  double lp = a.logp[b];
+  ResidentState<MAXIT> cs = resident_load<MAXIT>(c, a);
+  float (&x)[MAXIT] = cs.x; float (&g)[MAXIT] = cs.g; double& lp = cs.lp;
+  c.pads();
+  float xn[MAXIT];
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
-    const int j = lane + 64 * it;
-    x[it] = 0.f; g[it] = 0.f; xn[it] = 0.f;
-    if (j < d) { x[it] = a.pos[row + j]; g[it] = a.grad[row + j]; }
-  }
-  if (lane == 0) { xs[-1] = 0.f; xs[d] = 0.f; }
-  const Key2 kc = r.key_mode ? Key2{a.keys[2 * b], a.keys[2 * b + 1]} : Key2{0, 0};
+  for (int it = 0; it < MAXIT; ++it) xn[it] = 0.f;
+  const Key2 kc = run_chain_key(c, a, r.t);
   int n_acc = 0;
   double acc_sum = 0.0;
   DualAvg da = warmup_begin(a.eps);
   double eps = a.eps;                                     // the first step runs at the caller's value itself
 
-  for (int s = 0; s < r.n_steps; ++s) {
-    const Key2 kb = mcmc_run_key(r.key_mode, a.key, kc, (uint32_t)r.n_steps, (uint32_t)s, a.n_total, a.chain_offset + (uint32_t)b);
-    const Key2 k_int = mcmc_step_key(kb, MCMC_K_INT), k_rmh = mcmc_step_key(kb, MCMC_K_RMH);
+  for (int s = 0; s < r.t.n_steps; ++s) {
+    const Key2 kb = run_step_key(c, a, r.t, kc, s);
     if (w.step_traj && lane == 0) w.step_traj[(size_t)s * B + (size_t)b] = eps;
-    const double s2e = mala_s2e(eps);
-    double th1 = 0.0;                       // |x' - x - eps g|^2 = 2 eps |noise|^2
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int j = lane + 64 * it;
-      if (j < d) {
-        const double n = (double)(draw_t)run_normal64(k_int, (uint32_t)j, (uint32_t)d);
-        xn[it] = mala_propose<false>(x[it], g[it], n, eps, s2e, th1);
-        xs[j] = xn[it];
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the stencil reads its neighbours' proposal elements from this wave's row
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-
-    float gn[MAXIT];
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) gn[it] = 0.f;
-    const double lpn = row_value_grad<MAXIT, BCRT>(a.T, a.beta, xs, d, lane, gn, gsm);
-    double th2 = 0.0;                       // |x - x' - eps g'|^2
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      const int j = lane + 64 * it;
-      if (j < d) mala_back<false>(x[it], xn[it], gn[it], eps, th2);
-    }
-    th1 = wave_sum(th1); th2 = wave_sum(th2);
-    const double p = mala_accept_p<false>(lp, lpn, th1, th2, eps, a.textbook, RunExp());
-    const double u = run_uniform01(k_rmh);
-    const bool acc = u < p;
-    const double lpn0 = __shfl(lpn, 0, 64);     // the value a single-step launch stores (lane 0's) and the next one loads in every lane
-#pragma unroll
-    for (int it = 0; it < MAXIT; ++it) {
-      x[it] = acc ? xn[it] : x[it];
-      g[it] = acc ? gn[it] : g[it];
-    }
-    lp = acc ? lpn0 : lp;
+    MalaResident<MAXIT> st{x, g, lp, xn, false, 0.0, 0.0, 0.0};
+    mala_resident_step<MAXIT, BCRT>(a.T, a.beta, eps, mala_s2e(eps), a.textbook, kb, d, lane, xs, gsm, st);
+    const bool acc = st.acc;
+    const double p = st.p;
     warmup_tally(n_acc, acc_sum, acc, p);
     eps = warmup_next(da, s + 1, p, w.target);
-    // the next step overwrites the row (and the mixtures' gradient scratch) that other lanes of this wave have just read
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    resident_step_end();
   }
 
 #pragma unroll
-  for (int it = 0; it < MAXIT; ++it) {
+  for (int it = 0; it < MAXIT; ++it) {                    // (the final store stays in line: resident.hip.h)
     const int j = lane + 64 * it;
     if (j < d) { a.pos[row + j] = x[it]; a.grad[row + j] = g[it]; }
   }
-  const double avg = run_exp(da.xbar);
-  if (lane == 0) {
-    a.logp[b] = lp;
-    w.step_avg[b] = avg;
-    if (w.step_last) w.step_last[b] = eps;
-    if (r.n_acc) r.n_acc[b] = n_acc;
-    if (r.acc_sum) r.acc_sum[b] = acc_sum;
-  }
+  warmup_finish(c, r.t, w, da, eps, n_acc, acc_sum, a.logp, lp);
 }
 
 int launch_hmc_warmup(const HmcRunArgs& r, const WarmupArgs& w, hipStream_t stream) {

@@ -4,8 +4,8 @@
     python tools/isa_diff.py a.s b.s [--out profiles/NAME.txt]
 
 Both files are split by function symbol (`.type NAME,@function` up to its `.Lfunc_end`); comment lines and `;` comments are dropped
-and the function index in local labels (`.LBB<n>_`, `.Lfunc_end<n>`, ...) is normalised, so that a function which merely moved in
-the file compares equal.  Printed per function (kernels and out-of-line device functions), names demangled where c++filt is there:
+and the function index in local labels (`.LBB<n>_`, `.Lfunc_end<n>`, ...) and the file-wide counter of the long-branch labels
+(`.Lpost_getpc<n>`) are normalised, so that a function which merely moved in the file compares equal.  Printed per function (kernels and out-of-line device functions), names demangled where c++filt is there:
 `identical`, or `DIFFERS` with the resource lines of both sides (VGPRs, AGPRs, SGPRs, spills, scratch, LDS, occupancy) as the
 compiler states them in the comment block after the function; functions present on one side only are listed.  Exit status 0.
 """
@@ -36,6 +36,7 @@ def functions(path):
                     continue
                 code = line.split(";", 1)[0].strip()
                 if code and not code.startswith("//"):
+                    code = re.sub(r"\.Lpost_getpc\d+", ".Lpost_getpc#", code)      # (long branches: one counter over the whole file)
                     body.append(re.sub(r"\.L([A-Za-z_]+)\d+_", r".L\1#_", re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1#", code)))
             elif pending is not None:
                 m = re.match(r"\s*;\s*(\w+):\s*(\S+)", line)
