@@ -368,6 +368,46 @@ int mfm_autocorr(mfm_ctx* ctx, const float* d_x, int64_t n, int64_t n_series, in
                  float* d_tau, float* d_ess /* [n_series] or NULL; n_lags is then the max lag */,
                  double* d_mean, double* d_var /* [n_series] or NULL; var = A_0 / n */);
 
+/* ---- cross-chain diagnostics (diag.hip): split-R-hat and the multi-chain ("bulk") effective sample size of Gelman et al. / Stan.
+ *      d_x is float32 [n][n_chain_ld][dim], time-major, the layout of d_traj_pos; only chains 0 .. n_chain - 1 of every row are
+ *      read (a shard's padding rows are skipped without a copy).
+ *      Sub-chains.  split = 1: n_sub = n / 2 (integer division); sub-chain (m, 0) is rows [0, n_sub), sub-chain (m, 1) rows
+ *      [n - n_sub, n) (for odd n the middle row belongs to neither); M = 2 n_chain.  split = 0: n_sub = n, M = n_chain.
+ *      Per sub-chain c and coordinate j: mu_cj the float64 mean, A_k,cj = sum_{t < n_sub - k} c_t c_{t+k} of the signal centred by
+ *      ITS OWN mean -- the lag sums of the autocorrelation entry above, same arithmetic (float32 products inside
+ *      MFM_AUTOCORR_TIME_BLOCK steps, float64 across; MFM_AUTOCORR_F64=1: float64 throughout; float64 centring), A_0 in float64.
+ *      chain_sums writes d_sums, float64 [n_lags + 2][dim]:
+ *        sums[0][j] = sum_c mu_cj,   sums[1][j] = sum_c mu_cj^2,   sums[2 + k][j] = sum_c A_k,cj  (k = 0 .. n_lags - 1).
+ *      Every row is additive over disjoint sets of chains: chains sharded over ranks are combined by ONE all-reduce (sum) of this
+ *      array and of the sub-chain count.  No [n_lags][n_chain][dim] array exists anywhere; the scratch is context-owned, grown on
+ *      demand and independent of n: slabs [n_slices][n_lags + 2][dim] of float64 partial sums with n_slices = min(n_chain,
+ *      max(1, MFM_CHAIN_SLICES_MAX / ceil(dim / 64))) at most (at most 128 KiB (n_lags + 2) for dim <= 16384), and the mean and A_0
+ *      of every sub-chain and coordinate (2 float64 each: [2][M][dim]).  No floating-point atomics, one writer per element, a summation
+ *      order fixed by (n_chain, dim) alone: the same input gives the same bits on the same build, and the rows that a call with
+ *      fewer lags also has are the same bits in both.
+ *      chain_diag takes the (all-reduced) sums, n_sub and the TOTAL sub-chain count M = n_subchains, per coordinate in float64:
+ *        W      = sums[2] / (M (n_sub - 1))                          within-chain variance
+ *        B/n    = (sums[1] - sums[0]^2 / M) / (M - 1)                variance of the sub-chain means
+ *        var+   = (n_sub - 1) / n_sub * W + B/n
+ *        rhat   = sqrt(var+ / W)
+ *        rho_k  = 1 - (W - sums[2 + k] / (M (n_sub - 1))) / var+     (rho_0 = 1 - 0 exactly)
+ *        Gamma_m = rho_2m + rho_2m+1;  tau = -1 + 2 sum of Gamma_m over the leading run of Gamma_m > 0 among the pairs with
+ *        2m + 1 < n_lags: Geyer's rule exactly as in the autocorrelation entry, with NO monotone smoothing of the Gammas and NO
+ *        clamp of tau or ess (Stan applies both; an antithetic coordinate gives tau < 1 here);  ess = M n_sub / tau.
+ *      Outputs float32 [dim]: d_rhat, d_ess, d_tau, and d_rho [n_lags][dim]; each may be NULL, not all; rhat / ess / tau are the same
+ *      bits with and without d_rho.  Both calls are asynchronous on the context's stream and need no target, Fourier block or
+ *      parameters.
+ *      Edge semantics: a coordinate with W = 0 (constant in every sub-chain) gives NaN in all outputs of that coordinate only; a
+ *      non-finite input makes its own coordinate NaN and no other.  The subtraction in B/n cancels when |mean| >> the spread of the
+ *      sub-chain means: it is taken in float64, which leaves a relative error of about 1e-16 mean^2 / (B/n) in B/n.
+ *      EINVAL (message names the argument): n_sub < 2, n_chain < 1 or > n_chain_ld, dim < 1, n_subchains < 2, n_lags outside
+ *      [1, n_sub], split not 0 / 1, d_x / d_sums NULL, every output of chain_diag NULL. ---- */
+#define MFM_CHAIN_SLICES_MAX 256
+int mfm_chain_sums(mfm_ctx* ctx, const float* d_x, int64_t n, int32_t n_chain, int32_t n_chain_ld, int32_t dim, int32_t split,
+                   int32_t n_lags, double* d_sums /* [n_lags + 2][dim] */);
+int mfm_chain_diag(mfm_ctx* ctx, const double* d_sums, int64_t n_sub, int64_t n_subchains, int32_t dim, int32_t n_lags,
+                   float* d_rhat, float* d_ess, float* d_tau /* [dim] */, float* d_rho /* [n_lags][dim] */);
+
 /* ---- draws of the coming iterations, produced ahead of time (noise.hip) -------------------------------------------------
  * Slot j holds the Gaussian / uniform draws of the MALA step keyed h_keys_gn[j] and of the flow-matching batch keyed
  * h_keys_step[j] (uint32 [n_slots][2] each, the keys later passed to mfm_mala_step / mfm_fm_loss_grad).  The request arms

@@ -99,6 +99,8 @@ _SIGS = {
     "mfm_stein_disc": (C.c_int, [_P, _P, _P, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "mfm_max_mean_disc": (C.c_int, [_P, _P, _P, C.c_int, C.POINTER(C.c_double)]),
     "mfm_autocorr": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
+    "mfm_chain_sums": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mfm_chain_diag": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mfm_noise_prefetch": (C.c_int, [_P, C.c_int, C.POINTER(_U32), C.POINTER(_U32)]),
     "mfm_noise_drop": (C.c_int, [_P]),
     "mfm_get_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -612,6 +614,40 @@ class Context:
         n_series = int(x.numel() // n) if n else 0
         _chk(self.lib.mfm_autocorr(self.h, _ptr(x, F32), n, n_series, int(n if n_lags is None else n_lags), _ptr(rho, F32), _ptr(tau, F32),
                                    _ptr(ess, F32), _ptr(mean, F64), _ptr(var, F64)))
+
+    def chain_sums(self, x, sums, n_chain=None, split=True, chain_offset=0):
+        """``mfm_chain_sums`` on the float32 CUDA trajectory ``x [n, n_chain_ld, dim]`` (time-major, contiguous): the sums over the
+        sub-chains of chains ``chain_offset .. chain_offset + n_chain - 1`` (default: all from the offset on) into ``sums``, a float64
+        CUDA tensor ``[n_lags + 2, dim]`` whose first extent sets ``n_lags``.  Rows: sum of the sub-chain means, of their squares, of the
+        lag sums ``A_0 .. A_{n_lags-1}``; additive over disjoint sets of chains.  ``split``: both halves of every chain are sub-chains.
+        Returns ``(n_sub, n_subchains)``.  Asynchronous on the context's stream."""
+        if x.ndim != 3:
+            raise MfmError(f"chain_sums: expected a trajectory [n, n_chain, dim], got {tuple(x.shape)}")
+        if sums.ndim != 2 or sums.shape[0] < 3 or sums.shape[1] != x.shape[2]:
+            raise MfmError(f"chain_sums: sums must be [n_lags + 2, dim = {x.shape[2]}] with n_lags >= 1, got {tuple(sums.shape)}")
+        n, ld, dim = (int(v) for v in x.shape)
+        off = int(chain_offset)
+        if not 0 <= off < max(ld, 1):
+            raise MfmError(f"chain_sums: chain_offset must be in [0, {ld}) (got {off})")
+        n_chain = ld - off if n_chain is None else int(n_chain)
+        if off + n_chain > ld:                                       # (n_chain < 1 is the library's to refuse)
+            raise MfmError(f"chain_sums: chain_offset + n_chain = {off + n_chain} exceeds the {ld} chains of a row")
+        px = C.c_void_p((_ptr(x, F32).value or 0) + 4 * off * dim)         # (the row stride stays n_chain_ld * dim)
+        _chk(self.lib.mfm_chain_sums(self.h, px, n, n_chain, ld, dim, int(bool(split)), int(sums.shape[0]) - 2, _ptr(sums, F64)))
+        return (n // 2, 2 * n_chain) if split else (n, n_chain)
+
+    def chain_diag(self, sums, n_sub, n_subchains, rhat=None, ess=None, tau=None, rho=None):
+        """``mfm_chain_diag``: split-R-hat, multi-chain effective sample size and integrated autocorrelation time (float32 CUDA tensors
+        ``[dim]``) and optionally ``rho [n_lags, dim]`` from ``sums [n_lags + 2, dim]`` (float64, summed over the chains of every rank),
+        the sub-chain length ``n_sub`` and the TOTAL number of sub-chains.  Any subset of outputs, not none."""
+        if sums.ndim != 2 or sums.shape[0] < 3:
+            raise MfmError(f"chain_diag: sums must be [n_lags + 2, dim] with n_lags >= 1, got {tuple(sums.shape)}")
+        n_lags, dim = int(sums.shape[0]) - 2, int(sums.shape[1])
+        for name, t_, want in (("rhat", rhat, (dim,)), ("ess", ess, (dim,)), ("tau", tau, (dim,)), ("rho", rho, (n_lags, dim))):
+            if t_ is not None and tuple(t_.shape) != want:
+                raise MfmError(f"chain_diag: {name} must have shape {want}, got {tuple(t_.shape)}")
+        _chk(self.lib.mfm_chain_diag(self.h, _ptr(sums, F64), int(n_sub), int(n_subchains), dim, n_lags, _ptr(rhat, F32), _ptr(ess, F32),
+                                     _ptr(tau, F32), _ptr(rho, F32)))
 
     def beta_update(self, prev_beta, logliks, alpha):
         out = C.c_double()

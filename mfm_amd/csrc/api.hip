@@ -104,7 +104,8 @@ struct mfm_ctx {
   FmMala fuse_mala = {};                 // on != 0 during a mfm_train_iter whose MALA step rides in the training kernel
   int opt_resident_wgs = 0;              // workgroups of reduce_adamw_kernel this device holds at once (occupancy query at create)
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
-  void* run_ws = nullptr; size_t run_ws_cap = 0;   // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
+  void* cs_ws = nullptr; size_t cs_ws_cap = 0;     // mfm_chain_sums: mean and A_0 of every sub-chain, then the slabs [n_slices][n_lags + 2][dim] of float64 partial sums
+  void* run_ws = nullptr; size_t run_ws_cap = 0;  // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
   mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
   // mfm_hmc_set_inverse_mass: the diagonal of the HMC kernels' inverse mass matrix.  d_inv_mass [dim] holds the installed vector, or
   // ones when none is set (mfm_hmc_warmup_window runs the mass instances either way); h_inv_mass is the host copy, empty when none is set
@@ -395,7 +396,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->d_inv_mass};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -1573,7 +1574,46 @@ extern "C" int mfm_autocorr(mfm_ctx* x, const float* d_x, int64_t n, int64_t n_s
   return MFM_OK;
 }
 
-// ---- noise prefetch (noise.hip) -------------------------------------------------------------------------------------------
+extern "C" int mfm_chain_sums(mfm_ctx* x, const float* d_x, int64_t n, int32_t n_chain, int32_t n_chain_ld, int32_t dim, int32_t split, int32_t n_lags,
+                              double* d_sums) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (!d_sums) return fail(MFM_EINVAL, "d_sums is null");
+  if (split != 0 && split != 1) return fail(MFM_EINVAL, "split must be 0 or 1 (got %d)", split);
+  const int64_t n_sub = split ? n / 2 : n;
+  if (n_sub < 2) return fail(MFM_EINVAL, "n_sub must be at least 2 (n = %lld with split = %d gives n_sub = %lld)", (long long)n, split, (long long)n_sub);
+  if (n_chain_ld < 1 || n_chain < 1 || n_chain > n_chain_ld)
+    return fail(MFM_EINVAL, "n_chain must be in [1, n_chain_ld = %d] (got %d)", n_chain_ld, n_chain);
+  if (dim < 1) return fail(MFM_EINVAL, "dim must be at least 1 (got %d)", dim);
+  if (n_lags < 1 || n_lags > n_sub) return fail(MFM_EINVAL, "n_lags must be in [1, n_sub = %lld] (got %d)", (long long)n_sub, n_lags);
+  const ChainPlan q = chain_plan(n_chain, dim, n_lags);
+  const size_t need = (chain_stats_count(n_chain, dim, split) + (size_t)q.n_slices * ((size_t)n_lags + 2) * (size_t)dim) * sizeof(double);
+  if (x->cs_ws_cap < need) {
+    if (x->cs_ws) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(x->cs_ws); x->cs_ws = nullptr; x->cs_ws_cap = 0; }
+    HIPCHK(hipMalloc(&x->cs_ws, need));
+    x->cs_ws_cap = need;
+  }
+  if (launch_chain_sums(g_sw.autocorr_f64, d_x, n, n_chain, n_chain_ld, dim, split, n_lags, q, (double*)x->cs_ws, d_sums, x->stream))
+    return fail(MFM_ETOOLARGE, "dim = %d / n_lags = %d exceed the launch grid of the chain-sums kernel", dim, n_lags);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+extern "C" int mfm_chain_diag(mfm_ctx* x, const double* d_sums, int64_t n_sub, int64_t n_subchains, int32_t dim, int32_t n_lags, float* d_rhat, float* d_ess,
+                              float* d_tau, float* d_rho) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_sums) return fail(MFM_EINVAL, "d_sums is null");
+  if (n_sub < 2) return fail(MFM_EINVAL, "n_sub must be at least 2 (got %lld)", (long long)n_sub);
+  if (n_subchains < 2) return fail(MFM_EINVAL, "n_subchains must be at least 2 (got %lld)", (long long)n_subchains);
+  if (dim < 1) return fail(MFM_EINVAL, "dim must be at least 1 (got %d)", dim);
+  if (n_lags < 1 || n_lags > n_sub) return fail(MFM_EINVAL, "n_lags must be in [1, n_sub = %lld] (got %d)", (long long)n_sub, n_lags);
+  if (!d_rhat && !d_ess && !d_tau && !d_rho) return fail(MFM_EINVAL, "every output (d_rhat, d_ess, d_tau, d_rho) is null");
+  launch_chain_diag(d_sums, n_sub, n_subchains, dim, n_lags, d_rhat, d_ess, d_tau, d_rho, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+// ---- noise prefetch (noise.hip)-------------------------------------------------------------------------------------------
 extern "C" int mfm_noise_prefetch(mfm_ctx* x, int n_slots, const uint32_t* h_keys_gn, const uint32_t* h_keys_step) { use_ctx(x);
   NEED_TARGET();
   if (!h_keys_gn || !h_keys_step || n_slots <= 0) return fail(MFM_EINVAL, "bad arguments");

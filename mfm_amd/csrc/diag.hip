@@ -220,3 +220,169 @@ static int launch_autocorr(bool f64, const float* x, int64_t n, int64_t S, int L
   }
   return 0;
 }
+
+// ---- cross-chain sums: split-R-hat and the multi-chain effective sample size (mfm_chain_sums / mfm_chain_diag, include/mfm.h) -----------
+// Input x: float32 [n][n_chain_ld][dim]; chains 0 .. n_chain - 1 of every row are used.  Sub-chain (m, h) is the column of chain m over the
+// rows [0, n_sub) (h = 0) or [n - n_sub, n) (h = 1; split only).  Per sub-chain and coordinate: the float64 mean mu and the lag sums A_k
+// of the signal centred by ITS OWN mean -- lag_block above on (pointer, n_sub, row stride), unchanged, with A_0 replaced by the float64 sum
+// of autocorr_stats_kernel.  New here is the sum over sub-chains: sums [L + 2][dim] = (sum mu, sum mu^2, sum A_0, .., sum A_{L-1}).
+//
+// Mapping.  One wave (one workgroup) per (block of 64 coordinates, lag block, slice of chains); consecutive lanes on consecutive
+// coordinates, so a time row of a chain is one coalesced load for dim >= 64; for dim < 64 a wave lays 64 / dim chains side by side (lane
+// = chain-in-group * dim + coordinate) and a row of those chains is still one contiguous stretch.  The wave walks the chains of its slice
+// in index order, both halves of a chain in turn, and adds each sub-chain's A_k into float64 totals that live across the whole slice in
+// LDS (tot [AC_LB + 2][64], every lane its own column: no exchange, no barrier inside the loop; in registers they would take the lag
+// kernel past 256 VGPRs).  mu and A_0 come from chain_stats_kernel (2 doubles per sub-chain and coordinate): every lag block then does the same
+// work per sub-chain, so the lag blocks of a slice stay in step and share their rows in L2 as those of autocorr_lags_kernel do (with the
+// mean recomputed inside the wave, and A_0 by lag block 0 alone, block 0 fell behind the others: DESIGN.md section 4.13).  At the end the side-by-side chains of a coordinate are added in group order by the lane of group 0, and the
+// wave stores its rows of the slab [n_slices][L + 2][dim]; chain_sums_reduce_kernel adds the slabs in slice order.  No atomics, one writer
+// per element, a summation order fixed by (n_chain, dim) alone.  Workgroup ids are dealt as in autocorr_lags_kernel: the lag blocks of
+// a (coordinate block, slice) run together on one XCD.  Offsets are 64-bit.
+#define CS_SLICES_MAX MFM_CHAIN_SLICES_MAX    // cap of coordinate blocks x chain slices (include/mfm.h)
+
+// mean and A_0 of every sub-chain and coordinate in float64, the two passes of autocorr_stats_kernel; one lane per (chain, half, coordinate)
+// of the n_chain valid chains, stats [2][n_chain * n_half][dim]
+__global__ __launch_bounds__(64) void chain_stats_kernel(const float* __restrict__ x, int64_t n_sub, int64_t t1, int n_half, int64_t n_chain, int64_t S, int dim,
+                                                         double* __restrict__ stats) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x, n_rows = n_chain * n_half;
+  if (i >= n_rows * dim) return;
+  const int64_t m = i / dim, c = m / n_half;
+  const int j = (int)(i - m * dim), h = (int)(m - c * n_half);
+  const float* p = x + ((h ? t1 : 0) * S + c * dim + j);
+  double sum = 0.0;
+#pragma unroll 8
+  for (int64_t t = 0; t < n_sub; ++t) sum += (double)p[t * S];
+  const double mu = sum / (double)n_sub;
+  double a0 = 0.0;
+#pragma unroll 8
+  for (int64_t t = 0; t < n_sub; ++t) { const double cv = (double)p[t * S] - mu; a0 = fma(cv, cv, a0); }
+  stats[i] = mu;
+  stats[n_rows * dim + i] = a0;
+}
+
+struct ChainPlan { int n_cblocks, n_lblocks, n_slices, per_slice; int64_t n_units, grid; };
+static ChainPlan chain_plan(int n_chain, int dim, int L) {
+  ChainPlan q;
+  const int w = dim < 64 ? dim : 64, cpw = 64 / w;
+  q.n_cblocks = (dim + 63) / 64;
+  q.n_lblocks = (L + AC_LB - 1) / AC_LB;
+  // the slices depend on (n_chain, dim) and NOT on L: the order in which the chains are added, and with it every bit of the rows a call
+  // with fewer lags also has, is the same for every L.  Coordinate blocks x slices <= CS_SLICES_MAX: one wave per CU for every lag block.
+  int64_t want = CS_SLICES_MAX / q.n_cblocks;
+  if (want < 1) want = 1;
+  const int64_t groups = ((int64_t)n_chain + cpw - 1) / cpw;       // a group: the chains a wave holds side by side
+  if (want > groups) want = groups;
+  q.per_slice = (int)((groups + want - 1) / want) * cpw;
+  q.n_slices = (n_chain + q.per_slice - 1) / q.per_slice;          // (no empty slice)
+  q.n_units = (int64_t)q.n_cblocks * q.n_slices;
+  q.grid = (q.n_units + 7) / 8 * 8 * q.n_lblocks;
+  return q;
+}
+
+template <bool F64>
+__global__ __launch_bounds__(64, 2) void chain_sums_kernel(const float* __restrict__ x, int64_t n_sub, int64_t t1, int n_half, int n_chain, int64_t S,
+                                                           int dim, int L, int n_cblocks, int n_lblocks, int64_t n_units, int per_slice,
+                                                           const double* __restrict__ stats, double* __restrict__ slab) {
+  __shared__ double tot[AC_LB + 2][64];
+  const int64_t id = blockIdx.x, slot = id >> 3;
+  const int64_t unit = (slot / n_lblocks) * 8 + (id & 7);
+  if (unit >= n_units) return;                                      // (the grid is rounded up to 8 units)
+  const int lb = (int)(slot % n_lblocks), cb = (int)(unit % n_cblocks);
+  const int64_t slice = unit / n_cblocks, k0 = (int64_t)lb * AC_LB;
+  const int lane = threadIdx.x, w = dim < 64 ? dim : 64, cpw = 64 / w;
+  const int g = lane / w, j = cb * 64 + (lane - g * w), jc = j < dim ? j : dim - 1;      // idle lanes recompute the last coordinate
+  const bool lane_ok = g < cpw && j < dim;
+  const int64_t c0 = slice * per_slice;
+  const int64_t c1 = c0 + per_slice < n_chain ? c0 + per_slice : n_chain;
+#pragma unroll
+  for (int r = 0; r < AC_LB + 2; ++r) tot[r][lane] = 0.0;
+  for (int64_t cbase = c0; cbase < c1; cbase += cpw) {
+    const int64_t c = cbase + g, cc = c < c1 ? c : c1 - 1;         // ... and the last chain of the slice: never a chain past n_chain
+    const bool ok = lane_ok && c < c1;
+    for (int h = 0; h < n_half; ++h) {
+      const float* p = x + ((h ? t1 : 0) * S + cc * dim + jc);
+      const int64_t si = (cc * n_half + h) * dim + jc;
+      const double mu = stats[si];
+      double A[AC_LB];
+      lag_block<F64>(p, n_sub, S, k0, mu, A);
+      if (lb == 0) {
+        A[0] = stats[(int64_t)n_chain * n_half * dim + si];        // A_0 in float64
+        if (ok) { tot[0][lane] += mu; tot[1][lane] += mu * mu; }
+      }
+      if (ok) {
+#pragma unroll
+        for (int i = 0; i < AC_LB; ++i) tot[2 + i][lane] += A[i];
+      }
+    }
+  }
+  __syncthreads();
+  if (g == 0 && j < dim) {
+    double* out = slab + slice * ((int64_t)L + 2) * dim + j;
+    const int r0 = lb == 0 ? 0 : 2;
+    for (int r = r0; r < AC_LB + 2; ++r) {
+      const int64_t row = r < 2 ? r : 2 + k0 + (r - 2);
+      if (row >= (int64_t)L + 2) break;
+      double s = tot[r][lane];
+      for (int gg = 1; gg < cpw; ++gg) s += tot[r][lane + gg * w];
+      out[row * dim] = s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void chain_sums_reduce_kernel(const double* __restrict__ slab, int64_t n_elem, int n_slices, double* __restrict__ sums) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_elem) return;
+  double s = slab[i];
+  for (int64_t sl = 1; sl < n_slices; ++sl) s += slab[sl * n_elem + i];
+  sums[i] = s;
+}
+
+// R-hat, rho-hat, tau and ess of every coordinate from the sums over ALL sub-chains (include/mfm.h has the formulas); one lane per
+// coordinate, float64 throughout, Geyer's rule as in mfm_autocorr (leading run of positive pair sums: no monotone smoothing, no clamp)
+__global__ __launch_bounds__(64) void chain_diag_kernel(const double* __restrict__ sums, int64_t n_sub, int64_t M, int dim, int L, float* __restrict__ rhat,
+                                                        float* __restrict__ ess, float* __restrict__ tau, float* __restrict__ rho) {
+  const int j = blockIdx.x * 64 + threadIdx.x;
+  if (j >= dim) return;
+  const double Md = (double)M, den = Md * (double)(n_sub - 1), s0 = sums[j], s1 = sums[(int64_t)dim + j];
+  const double W = sums[2 * (int64_t)dim + j] / den;
+  const double Bn = (s1 - s0 * s0 / Md) / (Md - 1.0);
+  const double varp = (double)(n_sub - 1) / (double)n_sub * W + Bn;
+  const double inf = (double)__builtin_inff();
+  const bool bad = !(W > 0.0 && W < inf) || !(varp > -inf && varp < inf);
+  const float nanf_ = __builtin_nanf("");
+  if (rhat) rhat[j] = bad ? nanf_ : (float)sqrt(varp / W);
+  Geyer g = {0.0, bad};
+  int64_t k = 0;
+  for (; k + 1 < L; k += 2) {
+    if (g.done && !rho) break;
+    const double r0 = 1.0 - (W - sums[(2 + k) * dim + j] / den) / varp, r1 = 1.0 - (W - sums[(3 + k) * dim + j] / den) / varp;
+    if (rho) { rho[k * dim + j] = bad ? nanf_ : (float)r0; rho[(k + 1) * dim + j] = bad ? nanf_ : (float)r1; }
+    if (!g.done) { const double G = r0 + r1; if (G > 0.0) g.sum += G; else g.done = true; }
+  }
+  if (rho && k < L) rho[k * dim + j] = bad ? nanf_ : (float)(1.0 - (W - sums[(2 + k) * dim + j] / den) / varp);
+  const double t = bad ? (double)nanf_ : -1.0 + 2.0 * g.sum;
+  if (tau) tau[j] = (float)t;
+  if (ess) ess[j] = (float)(Md * (double)n_sub / t);
+}
+
+// ws: the stats [2][n_chain * n_half][dim], then the slab [plan.n_slices][L + 2][dim] (doubles).  Returns non-zero when a grid does not fit.
+static size_t chain_stats_count(int n_chain, int dim, int split) { return (size_t)2 * (size_t)n_chain * (split ? 2 : 1) * (size_t)dim; }
+static int launch_chain_sums(bool f64, const float* x, int64_t n, int n_chain, int n_chain_ld, int dim, int split, int L, const ChainPlan& q, double* ws,
+                             double* sums, hipStream_t stream) {
+  const int64_t n_sub = split ? n / 2 : n, S = (int64_t)n_chain_ld * dim, n_elem = ((int64_t)L + 2) * dim, g_red = (n_elem + 255) / 256;
+  const int n_half = split ? 2 : 1;
+  const int64_t g_stats = ((int64_t)n_chain * n_half * dim + 63) / 64;
+  if (q.grid > 0x7fffffffLL || g_red > 0x7fffffffLL || g_stats > 0x7fffffffLL) return 1;
+  double* stats = ws;
+  double* slab = ws + chain_stats_count(n_chain, dim, split);
+  hipLaunchKernelGGL(chain_stats_kernel, dim3((unsigned)g_stats), dim3(64), 0, stream, x, n_sub, n - n_sub, n_half, (int64_t)n_chain, S, dim, stats);
+  if (f64) hipLaunchKernelGGL(chain_sums_kernel<true>, dim3((unsigned)q.grid), dim3(64), 0, stream, x, n_sub, n - n_sub, n_half, n_chain, S, dim, L, q.n_cblocks,
+                              q.n_lblocks, q.n_units, q.per_slice, stats, slab);
+  else hipLaunchKernelGGL(chain_sums_kernel<false>, dim3((unsigned)q.grid), dim3(64), 0, stream, x, n_sub, n - n_sub, n_half, n_chain, S, dim, L, q.n_cblocks,
+                          q.n_lblocks, q.n_units, q.per_slice, stats, slab);
+  hipLaunchKernelGGL(chain_sums_reduce_kernel, dim3((unsigned)g_red), dim3(256), 0, stream, slab, n_elem, q.n_slices, sums);
+  return 0;
+}
+static void launch_chain_diag(const double* sums, int64_t n_sub, int64_t M, int dim, int L, float* rhat, float* ess, float* tau, float* rho, hipStream_t stream) {
+  hipLaunchKernelGGL(chain_diag_kernel, dim3((unsigned)((dim + 63) / 64)), dim3(64), 0, stream, sums, n_sub, M, dim, L, rhat, ess, tau, rho);
+}

@@ -451,6 +451,12 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         if use_hmc:
             logger.info("ESS per gradient evaluation of the HMC kernel (min, median, mean)= "
                         + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_grad_min", "ess_per_grad_median", "ess_per_grad_mean")))
+        logger.info(f"Split R-hat across chains (max, median over coordinates)= {ess_stats['rhat_max']:.4g}, {ess_stats['rhat_median']:.4g}")
+        logger.info(f"Multi-chain ESS per {step_name} and chain (min, median, mean over coordinates)= "
+                    + ", ".join(f"{ess_stats['ess_multichain_per_step_' + k]:.4g}" for k in ("min", "median", "mean")))
+        if use_hmc:
+            logger.info("Multi-chain ESS per gradient evaluation of the HMC kernel and chain (min, median, mean)= "
+                        + ", ".join(f"{ess_stats['ess_multichain_per_grad_' + k]:.4g}" for k in ("min", "median", "mean")))
         wandb.log(ess_stats)
     res = np.array([logpdf, stein[0], stein[1], mmd, train_time])                           # :561
     res_ = np.array([logpdf_, stein_[0], stein_[1], mmd_, train_time])
@@ -520,7 +526,10 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     An HMC step costs ``hmc_steps`` gradient evaluations where a MALA step costs one, so for ``hmc`` the same figures over
     ``hmc_steps`` come along as ``ess_per_grad_min`` / ``_median`` / ``_mean``: the scale on which the two kernels compare (for MALA
     it is ``ess_per_step_*`` itself).  The key is a child of ``key_gen`` that nothing else draws (``split(key_gen, 3)[2]``: the final
-    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are."""
+    sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are.
+    From the same trajectory, across the chains of all ranks (``diagnostics.chain_diagnostics``): ``rhat_max`` / ``rhat_median`` over the
+    coordinates, and the multi-chain ESS over (all chains x N) as ``ess_multichain_per_step_min`` / ``_median`` / ``_mean`` (for ``hmc`` also
+    ``ess_multichain_per_grad_*``)."""
     n_steps = int(getattr(args, "ess_steps", 0) or 0)
     if n_steps <= 0 or states.logdensity is None:                  # (training on exact samples keeps no MCMC state)
         return {}
@@ -540,6 +549,16 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     if use_hmc:
         for name in ("min", "median", "mean"):
             out["ess_per_grad_" + name] = out["ess_per_step_" + name] / int(args.hmc_steps)
+    # across the chains (of all ranks): split-R-hat and the multi-chain ESS, per step and chain (diagnostics.py; a chain stuck in one
+    # mode looks mixed to the per-chain figures above and not to these).  The padding rows past n_valid are skipped without a copy.
+    from . import diagnostics
+    cd = diagnostics.chain_diagnostics(info.positions, n_valid=eng.n_valid, ctx=eng.ctx)
+    rhat, multi = cd.rhat.double(), cd.ess.double() / (float(eng.n_total) * n_steps)
+    out.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item(), ess_multichain_per_step_min=multi.min().item(),
+               ess_multichain_per_step_median=multi.median().item(), ess_multichain_per_step_mean=multi.mean().item())
+    if use_hmc:
+        for name in ("min", "median", "mean"):
+            out["ess_multichain_per_grad_" + name] = out["ess_multichain_per_step_" + name] / int(args.hmc_steps)
     return out
 
 
