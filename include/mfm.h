@@ -184,6 +184,36 @@ int mfm_hmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const 
                 int32_t* d_n_accepted, double* d_acc_sum,
                 float* d_acceptance_rate, uint8_t* d_is_accepted,
                 float* d_traj_pos, double* d_traj_logp);
+/* BUILD-SIDE MODE like the HMC entry points: one transition of the No-U-turn sampler of every local chain (nuts.hip; tests/nuts_ref.py
+ * restates it).  Multinomial NUTS in the iterative, checkpointed form: momentum and leapfrog as mfm_hmc_step's (the installed inverse mass
+ * included, mfm_hmc_set_inverse_mass), the tree doubled at most max_tree_depth (1 .. 16) times in directions drawn from the chain's key,
+ * a leaf divergent when its energy exceeds the start's by more than divergence_threshold (> 0) or is NaN; the tree's proposal becomes
+ * the state, in place.  Info per chain (each may be NULL): d_depth int32, the completed doublings; d_num_leapfrog int32; d_is_turning /
+ * d_is_divergent uint8; d_acceptance_rate double, the mean of min(1, exp(H0 - H)) over every leaf integrated; d_energy double, the
+ * proposal's.  phi-four and mixture targets at dim <= 256: MFM_EUNSUPPORTED for the Cox process and for a larger dim.  The tree's
+ * U-turn checkpoints live in LDS; a max_tree_depth whose checkpoints exceed a CU's LDS returns MFM_EINVAL naming the largest that fits.
+ * A rejected call touches nothing. */
+int mfm_nuts_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, double step_size, int32_t max_tree_depth,
+                  double divergence_threshold, float* d_pos, double* d_logp, float* d_grad,
+                  int32_t* d_depth, int32_t* d_num_leapfrog, uint8_t* d_is_turning, uint8_t* d_is_divergent,
+                  double* d_acceptance_rate, double* d_energy);
+/* the same transition on the caller's OWN per-chain keys, uint32[n_chain_local][2], as mfm_hmc_step_keys */
+int mfm_nuts_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double step_size, int32_t max_tree_depth,
+                       double divergence_threshold, float* d_pos, double* d_logp, float* d_grad,
+                       int32_t* d_depth, int32_t* d_num_leapfrog, uint8_t* d_is_turning, uint8_t* d_is_divergent,
+                       double* d_acceptance_rate, double* d_energy);
+/* n_steps NUTS transitions in ONE launch, the chain resident in registers: bit-identical with n_steps single-step calls.  key_mode,
+ * keys, thin, d_traj_pos / d_traj_logp and their checks as mfm_hmc_run's.  Per-chain totals (each may be NULL): d_leapfrog_sum int64,
+ * leapfrog steps; d_acc_sum double, the sum of the transitions' acceptance rates; d_n_divergent int32, divergent transitions;
+ * d_depth_sum int32, the sum of the depths.  The info arrays take the LAST transition's. */
+int mfm_nuts_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                 double beta, double step_size, int32_t max_tree_depth, double divergence_threshold,
+                 int32_t n_steps, int32_t thin,
+                 float* d_pos, double* d_logp, float* d_grad,
+                 int64_t* d_leapfrog_sum, double* d_acc_sum, int32_t* d_n_divergent, int32_t* d_depth_sum,
+                 int32_t* d_depth, int32_t* d_num_leapfrog, uint8_t* d_is_turning, uint8_t* d_is_divergent,
+                 double* d_acceptance_rate, double* d_energy,
+                 float* d_traj_pos, double* d_traj_logp);
 /* STEP-SIZE WARMUP: n_steps steps of the HMC step (mfm_hmc_warmup) or of the MALA step under the textbook rule (mfm_mala_warmup) in
  * ONE launch, as mfm_hmc_run / mfm_mala_run (chain resident in registers, key_mode 0 / 1 and their key schedules), in which every
  * chain adapts its OWN step size by Nesterov dual averaging on its acceptance probability (Hoffman & Gelman 2014, algorithm 5).

@@ -66,6 +66,10 @@ _SIGS = {
     "mfm_hmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
     "mfm_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_nuts_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_nuts_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_nuts_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_hmc_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_mala_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_hmc_set_inverse_mass": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),
@@ -157,7 +161,7 @@ def _ptr(t, dtype=None):
     return C.c_void_p(t.data_ptr())
 
 
-F32, F64, U8, I32 = "float32", "float64", "uint8", "int32"
+F32, F64, U8, I32, I64 = "float32", "float64", "uint8", "int32", "int64"
 
 
 def _f32(a):
@@ -328,6 +332,41 @@ class Context:
                                   int(num_steps), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                   _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
                                   _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    def _nuts_info(self, depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy):
+        return (_ptr(depth, I32), _ptr(num_leapfrog, I32), _ptr(is_turning, U8), _ptr(is_divergent, U8), _ptr(acceptance_rate, F64), _ptr(energy, F64))
+
+    def nuts_step(self, key, beta, step_size, max_tree_depth, pos, logp, grad, divergence_threshold=1000.0, depth=None, num_leapfrog=None,
+                  is_turning=None, is_divergent=None, acceptance_rate=None, energy=None):
+        """Build-side mode (``mfm_nuts_step``): one No-U-turn transition of every local chain, state updated in place.  The info
+        tensors ``[n_chain_local]`` are optional: ``depth`` / ``num_leapfrog`` int32, the two flags uint8, ``acceptance_rate`` /
+        ``energy`` float64."""
+        _chk(self.lib.mfm_nuts_step(self.h, int(key[0]), int(key[1]), float(beta), float(step_size), int(max_tree_depth), float(divergence_threshold),
+                                    _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                    *self._nuts_info(depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy)))
+
+    def nuts_step_keys(self, keys, beta, step_size, max_tree_depth, pos, logp, grad, divergence_threshold=1000.0, depth=None, num_leapfrog=None,
+                       is_turning=None, is_divergent=None, acceptance_rate=None, energy=None):
+        """``mfm_nuts_step_keys``: ``keys`` is an int32/uint32 device tensor [n_chain_local, 2], one key per chain."""
+        _chk(self.lib.mfm_nuts_step_keys(self.h, _ptr(keys, I32), float(beta), float(step_size), int(max_tree_depth), float(divergence_threshold),
+                                         _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                         *self._nuts_info(depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy)))
+
+    def nuts_run(self, key, beta, step_size, max_tree_depth, n_steps, pos, logp, grad, divergence_threshold=1000.0, thin=0, leapfrog_sum=None,
+                 acc_sum=None, n_divergent=None, depth_sum=None, depth=None, num_leapfrog=None, is_turning=None, is_divergent=None,
+                 acceptance_rate=None, energy=None, traj_pos=None, traj_logp=None, key_mode=None):
+        """``mfm_nuts_run``: ``n_steps`` No-U-turn transitions in one launch, state updated in place; ``key`` / ``key_mode`` / ``thin`` /
+        the trajectory as ``hmc_run``'s.  Per-chain totals (optional): ``leapfrog_sum`` int64, ``acc_sum`` float64 (the sum of the
+        transitions' acceptance rates), ``n_divergent`` / ``depth_sum`` int32; the info tensors take the LAST transition's."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_nuts_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size),
+                                   int(max_tree_depth), float(divergence_threshold), int(n_steps), int(thin),
+                                   _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                   _ptr(leapfrog_sum, I64), _ptr(acc_sum, F64), _ptr(n_divergent, I32), _ptr(depth_sum, I32),
+                                   *self._nuts_info(depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy),
+                                   _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
 
     def _warmup_sizes(self, n_steps, step_avg, step_last, n_acc, acc_sum, step_traj):
         """The library cannot see a tensor's length: an output shorter than the kernel writes is refused here."""

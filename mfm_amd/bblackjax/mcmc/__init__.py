@@ -1,0 +1,1 @@
+from . import nuts  # noqa: F401

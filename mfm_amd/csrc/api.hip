@@ -16,6 +16,7 @@
 #include "lgcp.hip"
 #include "hmc.hip"
 #include "hmc_run.hip"
+#include "nuts.hip"
 #include "warmup.hip"
 #include "fm.hip"
 #include "optim.hip"
@@ -808,6 +809,67 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
   LAUNCHCHK();
   // steps only, next to mfm_hmc_step's: CTR_MALA_BYTES is the MALA kernels' traffic and covers no HMC entry point
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;
+  return MFM_OK;
+}
+
+// The No-U-turn sampler (nuts.hip).  Checks in mfm_hmc_run's order, then the tree's own: a rejected call touches nothing.
+static int nuts_args(mfm_ctx* x, NutsArgs& n, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t max_tree_depth,
+                     double div_thr, float* d_pos, double* d_logp, float* d_grad, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn, uint8_t* d_div,
+                     double* d_rate, double* d_energy) {
+  if (max_tree_depth < 1 || max_tree_depth > NUTS_MAX_DEPTH) return fail(MFM_EINVAL, "max_tree_depth must be in [1, %d] (got %d)", NUTS_MAX_DEPTH, max_tree_depth);
+  if (!(div_thr > 0)) return fail(MFM_EINVAL, "divergence_threshold must be positive (got %g)", div_thr);
+  if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "the NUTS step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)");
+  const int d = x->cfg.dim;
+  if (d > NUTS_MAX_DIM) return fail(MFM_EUNSUPPORTED, "the NUTS step serves dim <= %d (got %d): the larger instances need the tree's checkpoints outside LDS", NUTS_MAX_DIM, d);
+  const int waves = nuts_waves(d, max_tree_depth);
+  if (waves < 1) return fail(MFM_EINVAL, "max_tree_depth %d needs more LDS than a CU has at dim %d: the largest depth that fits is %d", max_tree_depth, d, nuts_depth_that_fits(d));
+  memset(&n, 0, sizeof n);
+  n.h = hmc_args(x, k0, k1, d_keys, beta, step, 0, d_pos, d_logp, d_grad, nullptr, nullptr);
+  n.max_depth = max_tree_depth; n.waves = waves; n.div_thr = div_thr;
+  n.depth = d_depth; n.n_leap = d_nleap; n.turning = d_turn; n.divergent = d_div; n.acc_rate = d_rate; n.energy = d_energy;
+  return MFM_OK;
+}
+static int nuts_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t max_tree_depth, double div_thr,
+                            float* d_pos, double* d_logp, float* d_grad, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn, uint8_t* d_div,
+                            double* d_rate, double* d_energy) {
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  NutsArgs n;
+  CHECKED(nuts_args(x, n, k0, k1, d_keys, beta, step, max_tree_depth, div_thr, d_pos, d_logp, d_grad, d_depth, d_nleap, d_turn, d_div, d_rate, d_energy));
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_nuts_step(n, x->stream)) return too_large(x, "NUTS");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += x->cfg.n_chain_local;      // (steps only, as mfm_hmc_step)
+  return MFM_OK;
+}
+extern "C" int mfm_nuts_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, int32_t max_tree_depth, double div_thr, float* d_pos,
+                             double* d_logp, float* d_grad, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn, uint8_t* d_div, double* d_rate,
+                             double* d_energy) { use_ctx(x);
+  return nuts_step_common(x, k0, k1, nullptr, beta, step, max_tree_depth, div_thr, d_pos, d_logp, d_grad, d_depth, d_nleap, d_turn, d_div, d_rate, d_energy);
+}
+extern "C" int mfm_nuts_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, double step, int32_t max_tree_depth, double div_thr, float* d_pos,
+                                  double* d_logp, float* d_grad, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn, uint8_t* d_div, double* d_rate,
+                                  double* d_energy) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return nuts_step_common(x, 0, 0, d_keys, beta, step, max_tree_depth, div_thr, d_pos, d_logp, d_grad, d_depth, d_nleap, d_turn, d_div, d_rate, d_energy);
+}
+extern "C" int mfm_nuts_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t max_tree_depth,
+                            double div_thr, int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int64_t* d_tot_leap,
+                            double* d_acc_sum, int32_t* d_n_div, int32_t* d_depth_sum, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn,
+                            uint8_t* d_div, double* d_rate, double* d_energy, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  NutsRunArgs r; memset(&r, 0, sizeof r);
+  CHECKED(nuts_args(x, r.n, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, max_tree_depth, div_thr, d_pos, d_logp, d_grad, d_depth, d_nleap,
+                    d_turn, d_div, d_rate, d_energy));
+  r.t = RunTail{key_mode, n_steps, thin, nullptr, nullptr, d_traj_pos, d_traj_logp};
+  r.tot_leap = d_tot_leap; r.tot_acc = d_acc_sum; r.tot_div = d_n_div; r.tot_depth = d_depth_sum;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_nuts_run(r, x->stream)) return too_large(x, "NUTS");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
   return MFM_OK;
 }
 

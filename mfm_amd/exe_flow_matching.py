@@ -221,6 +221,9 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
         eng.ctx.cis_select(rng_key, n_is, u0, vol0, refs, xs, vols, lps, pos, logp, info["acc"], info["isacc"], info["prop"], info["w"])
 
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
+    use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
+    if use_nuts:
+        info["nuts_acc"] = t.empty(n, device=eng.dev, dtype=t.float64)
 
     def train_data_generator(rng_key, states, count, vector_field_param=None, beta=1.0):
         """:300-314.  States are updated IN PLACE (and returned); infos are views of reused device buffers."""
@@ -237,6 +240,9 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
             eng.ctx.flow_step(mode, rng_key, beta, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["nsteps"])
         elif use_hmc:          # build-side mode (--mcmc_kernel hmc): the iteration's MCMC move is an HMC step (mfm_hmc_step) instead of :313
             eng.ctx.hmc_step(rng_key, beta, args.step_size, int(args.hmc_steps), pos, logp, grad, info["acc"], info["isacc"])
+        elif use_nuts:         # build-side mode (--mcmc_kernel nuts): a No-U-turn transition (mfm_nuts_step); it always takes its tree's proposal
+            eng.ctx.nuts_step(rng_key, beta, args.step_size, int(getattr(args, "max_tree_depth", 10)), pos, logp, grad, acceptance_rate=info["nuts_acc"])
+            info["acc"].copy_(info["nuts_acc"]); info["isacc"].fill_(1)
         else:
             eng.ctx.mala_step(rng_key, beta, args.step_size, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["w"])
         return MALAState(pos, logp, grad), MALAInfo(info["acc"], info["isacc"], info["prop"], info["w"])
@@ -252,7 +258,7 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
     train_data_generator.info_buffers = info
     # what run() needs to issue generator + train_step as ONE library call (mfm_train_iter) where that is the same computation
     train_data_generator.flow_mode = mode
-    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc
+    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc and not use_nuts
     return train_data_generator, init_fn, transform_and_logdet
 
 
@@ -445,17 +451,21 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     ess_stats = chain_ess_per_step(eng, dist, args, train_states, key_gen)                  # --ess_steps (build-side addition; {} at 0)
     if ess_stats:
         use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
-        step_name = f"HMC step ({int(args.hmc_steps)} leapfrog steps)" if use_hmc else "MALA step"
+        use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
+        step_name = f"HMC step ({int(args.hmc_steps)} leapfrog steps)" if use_hmc else "NUTS transition" if use_nuts else "MALA step"
         logger.info(f"ESS per {step_name} (min, median, mean over chains and coordinates)= "
                     + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_step_min", "ess_per_step_median", "ess_per_step_mean")))
-        if use_hmc:
-            logger.info("ESS per gradient evaluation of the HMC kernel (min, median, mean)= "
+        if use_nuts:
+            logger.info(f"NUTS trees over the run: mean depth= {ess_stats['nuts_mean_depth']:.4g}, mean leapfrog steps= {ess_stats['nuts_mean_leapfrog']:.4g}, "
+                        f"divergent transitions= {ess_stats['nuts_divergent']}")
+        if use_hmc or use_nuts:
+            logger.info(f"ESS per gradient evaluation of the {'HMC' if use_hmc else 'NUTS'} kernel (min, median, mean)= "
                         + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_grad_min", "ess_per_grad_median", "ess_per_grad_mean")))
         logger.info(f"Split R-hat across chains (max, median over coordinates)= {ess_stats['rhat_max']:.4g}, {ess_stats['rhat_median']:.4g}")
         logger.info(f"Multi-chain ESS per {step_name} and chain (min, median, mean over coordinates)= "
                     + ", ".join(f"{ess_stats['ess_multichain_per_step_' + k]:.4g}" for k in ("min", "median", "mean")))
-        if use_hmc:
-            logger.info("Multi-chain ESS per gradient evaluation of the HMC kernel and chain (min, median, mean)= "
+        if use_hmc or use_nuts:
+            logger.info(f"Multi-chain ESS per gradient evaluation of the {'HMC' if use_hmc else 'NUTS'} kernel and chain (min, median, mean)= "
                         + ", ".join(f"{ess_stats['ess_multichain_per_grad_' + k]:.4g}" for k in ("min", "median", "mean")))
         wandb.log(ess_stats)
     res = np.array([logpdf, stein[0], stein[1], mmd, train_time])                           # :561
@@ -470,7 +480,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
 
 
 def check_adapt_args(args):
-    """``--adapt_steps`` needs ``--mcmc_kernel hmc`` and a run that takes MCMC steps: raised before any device work."""
+    """``--adapt_steps`` needs ``--mcmc_kernel hmc`` (or ``nuts``, which runs the HMC warmup) and a run that takes MCMC steps: raised before any device work."""
     n_steps = int(getattr(args, "adapt_steps", 0) or 0)
     if n_steps < 0:
         raise ValueError(f"--adapt_steps must not be negative (got {n_steps})")
@@ -478,7 +488,7 @@ def check_adapt_args(args):
         raise ValueError("--adapt_mass adapts the mass matrix during the --adapt_steps N warmup steps: give N > 0")
     if n_steps > 0 and args.mcmc_per_flow_steps < 0:
         raise ValueError("--adapt_steps has nothing to adapt with mcmc_per_flow_steps < 0: that run trains on exact samples and takes no MCMC step")
-    if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") != "hmc":
+    if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") not in ("hmc", "nuts"):
         raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
                          "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
     return n_steps
@@ -496,7 +506,10 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     ``--adapt_mass``: the N steps run ``window_adaptation`` (``bblackjax/adaptation/window_adaptation.py``) instead, on the same key and
     copy: step size and a diagonal mass matrix together.  The inverse mass matrix is installed on the engine's context, where the
     training loop's ``hmc_step`` calls find it, and kept as ``args.inverse_mass_matrix`` for ``--ess_steps``; besides the two figures
-    above (``adapt_acceptance``: of the last segment) the result carries ``adapted_inverse_mass`` (the vector) and its ``_min`` / ``_max``."""
+    above (``adapt_acceptance``: of the last segment) the result carries ``adapted_inverse_mass`` (the vector) and its ``_min`` / ``_max``.
+
+    ``--mcmc_kernel nuts``: the same HMC warmup with ``--hmc_steps`` leapfrog steps, whose step size and mass NUTS then samples with -- the
+    integrator and the metric are the same; it approximates adapting on the tree's own acceptance statistic."""
     n_steps = check_adapt_args(args)
     if n_steps <= 0:
         return {}
@@ -529,16 +542,23 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     sampling uses ``split(key_gen)`` and ``split(key_gen, n_final)``), and the chains of ``states`` are left as they are.
     From the same trajectory, across the chains of all ranks (``diagnostics.chain_diagnostics``): ``rhat_max`` / ``rhat_median`` over the
     coordinates, and the multi-chain ESS over (all chains x N) as ``ess_multichain_per_step_min`` / ``_median`` / ``_mean`` (for ``hmc`` also
-    ``ess_multichain_per_grad_*``)."""
+    ``ess_multichain_per_grad_*``).
+    ``--mcmc_kernel nuts``: N No-U-turn transitions (``nuts(...).step.run``); a transition costs its tree's leapfrog steps, so ``ess_per_grad_*``
+    and ``ess_multichain_per_grad_*`` divide by the MEASURED mean leapfrog count per transition over the run and the chains of all ranks,
+    logged as ``nuts_mean_leapfrog`` beside ``nuts_mean_depth`` and ``nuts_divergent`` (the number of divergent transitions)."""
     n_steps = int(getattr(args, "ess_steps", 0) or 0)
     if n_steps <= 0 or states.logdensity is None:                  # (training on exact samples keeps no MCMC state)
         return {}
     import torch
     from . import mcmc_utils
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
+    use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
     if use_hmc:
         from .bblackjax.mcmc.hmc import hmc
         algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps), getattr(args, "inverse_mass_matrix", None))      # (--adapt_mass)
+    elif use_nuts:
+        from .bblackjax.mcmc.nuts import nuts
+        algo = nuts(dist.logprob, args.step_size, int(getattr(args, "max_tree_depth", 10)), getattr(args, "inverse_mass_matrix", None))
     else:
         from .bblackjax.mcmc.mala import mala
         algo = mala(dist.logprob, args.step_size)
@@ -546,9 +566,17 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     ess, _ = mcmc_utils.effective_sample_size(info.positions[:, :eng.n_valid], ctx=eng.ctx)
     per_step = (ess.double() / n_steps).reshape(-1)
     out = dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
-    if use_hmc:
+    grads_per_step = float(int(args.hmc_steps)) if use_hmc else 1.0
+    if use_nuts:       # a transition costs its tree's leapfrog steps: the measured mean over the run's transitions and the chains of all ranks
+        from .engine import global_mean_std
+        per_chain = torch.stack([info.num_integration_steps.double() / n_steps, info.mean_trajectory_expansions.double(),
+                                           info.num_divergent.double()], 1)[:eng.n_valid]
+        means = [global_mean_std(per_chain[:, q].contiguous(), eng.n_total)[0].item() for q in range(3)]
+        grads_per_step = means[0]
+        out.update(nuts_mean_leapfrog=means[0], nuts_mean_depth=means[1], nuts_divergent=int(round(means[2] * eng.n_total)))
+    if use_hmc or use_nuts:
         for name in ("min", "median", "mean"):
-            out["ess_per_grad_" + name] = out["ess_per_step_" + name] / int(args.hmc_steps)
+            out["ess_per_grad_" + name] = out["ess_per_step_" + name] / grads_per_step
     # across the chains (of all ranks): split-R-hat and the multi-chain ESS, per step and chain (diagnostics.py; a chain stuck in one
     # mode looks mixed to the per-chain figures above and not to these).  The padding rows past n_valid are skipped without a copy.
     from . import diagnostics
@@ -556,9 +584,9 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     rhat, multi = cd.rhat.double(), cd.ess.double() / (float(eng.n_total) * n_steps)
     out.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item(), ess_multichain_per_step_min=multi.min().item(),
                ess_multichain_per_step_median=multi.median().item(), ess_multichain_per_step_mean=multi.mean().item())
-    if use_hmc:
+    if use_hmc or use_nuts:
         for name in ("min", "median", "mean"):
-            out["ess_multichain_per_grad_" + name] = out["ess_multichain_per_step_" + name] / int(args.hmc_steps)
+            out["ess_multichain_per_grad_" + name] = out["ess_multichain_per_step_" + name] / grads_per_step
     return out
 
 

@@ -3,7 +3,7 @@ overrides, ``multi_modal.py:21-101,147-220``), running the MFM loop on MI355X.
 
 Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / ``--force_num_chain`` override the
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
-``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` also per gradient evaluation),
+``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
 ``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows),
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); the other baselines
@@ -155,8 +155,10 @@ def build_parser():
     parser.add_argument('--ode_steps', type=int, default=0)
     # the MCMC move of a non-flow iteration: the reference's MALA step (exe_flow_matching.py:313), or -- BASELINE.json's "MALA/HMC" step,
     # not in the reference -- an HMC step of --hmc_steps velocity-Verlet steps of size --step_size (mfm_amd/bblackjax/mcmc/hmc.py)
-    parser.add_argument('--mcmc_kernel', type=str, default='mala', choices=['mala', 'hmc'])
+    parser.add_argument('--mcmc_kernel', type=str, default='mala', choices=['mala', 'hmc', 'nuts'])
     parser.add_argument('--hmc_steps', type=int, default=10)
+    # 'nuts': a No-U-turn transition of step size --step_size whose tree doubles at most --max_tree_depth times (mfm_amd/bblackjax/mcmc/nuts.py)
+    parser.add_argument('--max_tree_depth', type=int, default=10)
     # the phi-four lattice's boundary (distributions.py:114-139; the reference's main script builds Dirichlet 0): both ends held at
     # --phi4_bc_value, or a periodic ring (--phi4_bc pbc; the value is ignored)
     parser.add_argument('--phi4_bc', type=str, default='dirichlet', choices=['dirichlet', 'pbc'])
