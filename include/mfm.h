@@ -271,6 +271,34 @@ int mfm_hmc_warmup_window(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t ke
                           int32_t* d_n_accepted, double* d_acc_sum,
                           double* d_step_traj,
                           double* d_pos_sum, double* d_pos_sumsq);
+/* STEP-SIZE WARMUP OF THE NO-U-TURN SAMPLER: n_steps NUTS transitions in ONE launch, as mfm_nuts_run (chain resident in registers,
+ * key_mode 0 / 1 and their key schedules, max_tree_depth / divergence_threshold and the installed inverse mass as there), in which every
+ * chain adapts its OWN step size by the dual averaging of mfm_hmc_warmup -- the same recursion, constants and clamp, eps_1 = step0
+ * itself -- on p_m = its tree's acceptance statistic: the mean over every leaf integrated of min(1, exp(H0 - H)), the float64 value
+ * mfm_nuts_step reports as d_acceptance_rate.  Outputs per chain: d_step_avg (required), d_step_last, d_step_traj double[n_steps][B] as
+ * mfm_hmc_warmup's; d_acc_sum double, the sum of the p_m in step order (a transition has no accept / reject: there is no d_n_accepted);
+ * d_leapfrog_sum int64, d_n_divergent int32, d_depth_sum int32 as mfm_nuts_run's (each may be NULL).  Transition m of chain b has the
+ * bits of mfm_nuts_step_keys with the scalar step size d_step_traj[m][b] and the same step key.  Chains at different step sizes build
+ * trees of different depths, and the launch ends with its slowest chain.  No trajectory and no last-step info are kept.
+ * Errors: mfm_hmc_warmup's (n_steps, step_size, target_accept, key_mode, d_keys, d_step_avg), then mfm_nuts_step's (max_tree_depth,
+ * divergence_threshold, MFM_EUNSUPPORTED for the Cox process and for dim > 256, the LDS limit).  A rejected call touches nothing. */
+int mfm_nuts_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                    double beta, double step0, int32_t max_tree_depth, double divergence_threshold,
+                    int32_t n_steps, double target_accept,
+                    float* d_pos, double* d_logp, float* d_grad,
+                    double* d_step_avg, double* d_step_last, double* d_acc_sum, double* d_step_traj,
+                    int64_t* d_leapfrog_sum, int32_t* d_n_divergent, int32_t* d_depth_sum);
+/* ONE WINDOW of a mass-matrix adaptation under NUTS: mfm_nuts_warmup, which also adds the state after every transition, the float32
+ * position as a double, in step order to d_pos_sum double[B][dim] and its (exact) square to d_pos_sumsq double[B][dim]; both are required
+ * and are overwritten.  As mfm_hmc_warmup_window it always runs the mass instances, with the context's vector, or with ones when none is
+ * installed: everything else it writes then has mfm_nuts_warmup's bits. */
+int mfm_nuts_warmup_window(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                           double beta, double step0, int32_t max_tree_depth, double divergence_threshold,
+                           int32_t n_steps, double target_accept,
+                           float* d_pos, double* d_logp, float* d_grad,
+                           double* d_step_avg, double* d_step_last, double* d_acc_sum, double* d_step_traj,
+                           int64_t* d_leapfrog_sum, int32_t* d_n_divergent, int32_t* d_depth_sum,
+                           double* d_pos_sum, double* d_pos_sumsq);
 /* vmap(dist.loglik) (exe_flow_matching.py:418) */
 int mfm_loglik(mfm_ctx* ctx, const float* d_pos, double* d_out);
 

@@ -75,6 +75,10 @@ _SIGS = {
     "mfm_hmc_set_inverse_mass": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32]),
     "mfm_hmc_get_inverse_mass": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "mfm_hmc_warmup_window": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_nuts_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_double, _P, _P, _P,
+                                  _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_nuts_warmup_window": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_double, _P, _P, _P,
+                                         _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_loglik": (C.c_int, [_P, _P, _P]),
     "mfm_smc_delta": (C.c_int, [_P, _P, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "mfm_smc_weights": (C.c_int, [_P, _P, C.c_int, C.c_double, _P, C.POINTER(C.c_double)]),
@@ -442,6 +446,45 @@ class Context:
         _chk(self.lib.mfm_mala_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
                                       int(textbook), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                       _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
+
+    def _nuts_warmup_args(self, key, beta, step0, max_tree_depth, n_steps, target_accept, pos, logp, grad, step_avg, divergence_threshold,
+                          step_last, acc_sum, step_traj, leapfrog_sum, n_divergent, depth_sum, key_mode):
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        self._warmup_sizes(n_steps, step_avg, step_last, None, acc_sum, step_traj)
+        for name, t_ in (("leapfrog_sum", leapfrog_sum), ("n_divergent", n_divergent), ("depth_sum", depth_sum)):
+            if t_ is not None and t_.numel() < self.n_local:
+                raise MfmError(f"{name} must hold n_chain_local = {self.n_local} elements (got {t_.numel()})")
+        return (self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0), int(max_tree_depth),
+                float(divergence_threshold), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(acc_sum, F64), _ptr(step_traj, F64),
+                _ptr(leapfrog_sum, I64), _ptr(n_divergent, I32), _ptr(depth_sum, I32))
+
+    def nuts_warmup(self, key, beta, step0, max_tree_depth, n_steps, target_accept, pos, logp, grad, step_avg, divergence_threshold=1000.0,
+                    step_last=None, acc_sum=None, step_traj=None, leapfrog_sum=None, n_divergent=None, depth_sum=None, key_mode=None):
+        """``mfm_nuts_warmup``: ``n_steps`` No-U-turn transitions in one launch, every chain adapting its own step size from ``step0`` by
+        the dual averaging of ``hmc_warmup`` on its tree's acceptance statistic (the mean over the leaves of ``min(1, exp(H0 - H))``);
+        state updated in place.  ``key`` / ``key_mode`` as ``nuts_run``'s.  ``step_avg`` (float64 ``[n_chain_local]``, required) takes the
+        averaged step size, the result; ``step_last`` the last iterate; ``step_traj`` (float64 ``[n_steps, n_chain_local]``) the step
+        size used at every transition; ``acc_sum`` float64 the sum of the statistics; ``leapfrog_sum`` int64, ``n_divergent`` /
+        ``depth_sum`` int32 as ``nuts_run``'s."""
+        _chk(self.lib.mfm_nuts_warmup(*self._nuts_warmup_args(key, beta, step0, max_tree_depth, n_steps, target_accept, pos, logp, grad, step_avg,
+                                                              divergence_threshold, step_last, acc_sum, step_traj, leapfrog_sum, n_divergent,
+                                                              depth_sum, key_mode)))
+
+    def nuts_warmup_window(self, key, beta, step0, max_tree_depth, n_steps, target_accept, pos, logp, grad, step_avg, pos_sum, pos_sumsq,
+                           divergence_threshold=1000.0, step_last=None, acc_sum=None, step_traj=None, leapfrog_sum=None, n_divergent=None,
+                           depth_sum=None, key_mode=None):
+        """``mfm_nuts_warmup_window``: ``nuts_warmup`` on the mass instances (the installed vector, or ones), which also leaves in
+        ``pos_sum`` / ``pos_sumsq`` (float64 ``[n_chain_local, dim]``, both required) the sums over the transitions of every chain's
+        position and of its square, as ``hmc_warmup_window`` does."""
+        args = self._nuts_warmup_args(key, beta, step0, max_tree_depth, n_steps, target_accept, pos, logp, grad, step_avg, divergence_threshold,
+                                      step_last, acc_sum, step_traj, leapfrog_sum, n_divergent, depth_sum, key_mode)
+        for name, t_ in (("pos_sum", pos_sum), ("pos_sumsq", pos_sumsq)):
+            if t_ is not None and t_.numel() < self.n_local * self.dim:
+                raise MfmError(f"{name} must hold n_chain_local * dim = {self.n_local * self.dim} elements (got {t_.numel()})")
+        _chk(self.lib.mfm_nuts_warmup_window(*args, _ptr(pos_sum, F64), _ptr(pos_sumsq, F64)))
 
     def loglik(self, pos, out):
         _chk(self.lib.mfm_loglik(self.h, _ptr(pos, F32), _ptr(out, F64)))

@@ -7,14 +7,17 @@ caller's own keys ``[n_chain_local, 2]``, ``logdensity_fn`` built from a device 
 vector ``[dim]`` (a call's mass is its argument: every launch installs or clears it first).  The integrator and the metric are HMC's,
 so a step size and a mass adapted by ``hmc(...).step.warmup`` / ``adaptation.window_adaptation`` carry over.  The kernel carries
 ``kernel.run(rng_key, state, logdensity_fn, step_size, num_steps, thin=0, ...)``: ``num_steps`` transitions in ONE launch with the
-chain resident on the device, bit-identical with the loop of single steps (key schedule: ``hmc.py``)."""
+chain resident on the device, bit-identical with the loop of single steps (key schedule: ``hmc.py``), and ``kernel.warmup(rng_key,
+state, logdensity_fn, step_size, num_steps, target_acceptance_rate=0.8, return_step_sizes=False, ...)``: ``num_steps`` transitions in one
+launch (``mfm_nuts_warmup``) in which every chain adapts its own step size from ``step_size`` by dual averaging on its tree's acceptance
+statistic -- NUTS tunes itself, no ``num_integration_steps`` has to be chosen (``adaptation.nuts_window_adaptation`` adds the mass)."""
 from typing import Callable, NamedTuple
 
 from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 from .hmc import HMCState as NUTSState, _device_keys, _mass_engine, check_inverse_mass, init
 
-__all__ = ["NUTSState", "NUTSInfo", "NUTSRunInfo", "init", "build_kernel", "nuts"]
+__all__ = ["NUTSState", "NUTSInfo", "NUTSRunInfo", "NUTSWarmupInfo", "init", "build_kernel", "nuts"]
 
 
 class NUTSInfo(NamedTuple):
@@ -40,6 +43,21 @@ class NUTSRunInfo(NamedTuple):
     last: NUTSInfo
     positions: object
     logdensities: object
+
+
+class NUTSWarmupInfo(NamedTuple):
+    """What ``kernel.warmup`` reports.  Per chain (``[n_chain_local]``): ``step_size`` (float64), the averaged iterate ``exp(xbar_n)`` --
+    the result; ``pooled_step_size``, ONE float, the geometric mean of ``step_size`` over the chains of all ranks without the padding
+    rows (``mcmc_utils.pooled_step_size``); per chain the mean over the warmup of the trees' acceptance statistic, the leapfrog steps
+    (int64), the divergent transitions and the mean depth; ``step_sizes [num_steps, n_chain_local]``, the step size USED at every
+    transition (``None`` unless asked for)."""
+    step_size: object
+    pooled_step_size: float
+    acceptance_rate: object
+    num_integration_steps: object
+    num_divergent: object
+    mean_depth: object
+    step_sizes: object
 
 
 def _info_buffers(t, n, dev):
@@ -96,7 +114,35 @@ def build_kernel():
                          traj_logp=traj_logp, **buf)
         return NUTSState(pos, logp, grad), NUTSRunInfo(acc_sum / num_steps, leap, n_div, depth_sum.double() / num_steps, _info(buf), traj_pos, traj_logp)
 
+    def warmup(rng_key, state: NUTSState, logdensity_fn: Callable, step_size: float, num_steps: int, target_acceptance_rate: float = 0.8,
+               return_step_sizes: bool = False, max_num_doublings: int = 10, inverse_mass_matrix=None, divergence_threshold: float = 1000.0):
+        """``num_steps`` transitions in one launch, from ``step_size``, every chain adapting its own step size towards
+        ``target_acceptance_rate`` on its tree's acceptance statistic; keys as ``run``'s (one key: step-major; ``[n_chain_local, 2]``:
+        chain-major).  Returns the state after the transitions and a ``NUTSWarmupInfo``; ``info.pooled_step_size`` is the value to
+        sample with."""
+        from ...mcmc_utils import pooled_step_size
+        dist, beta = resolve_logdensity(logdensity_fn)
+        eng = _mass_engine(dist, inverse_mass_matrix)
+        t = eng.torch
+        num_steps = int(num_steps)
+        pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()      # states are values
+        n, dev = pos.shape[0], pos.device
+        step_avg = t.empty(n, device=dev, dtype=t.float64)
+        acc_sum = t.empty(n, device=dev, dtype=t.float64)
+        leap = t.empty(n, device=dev, dtype=t.int64)
+        n_div = t.empty(n, device=dev, dtype=t.int32)
+        depth_sum = t.empty(n, device=dev, dtype=t.int32)
+        traj = t.empty((num_steps, n), device=dev, dtype=t.float64) if return_step_sizes and num_steps >= 1 else None
+        if getattr(rng_key, "ndim", 1) == 2:
+            rng_key = _device_keys(t, rng_key, dev)
+        eng.ctx.nuts_warmup(rng_key, beta, step_size, max_num_doublings, num_steps, target_acceptance_rate, pos, logp, grad, step_avg,
+                            divergence_threshold=divergence_threshold, acc_sum=acc_sum, step_traj=traj, leapfrog_sum=leap, n_divergent=n_div,
+                            depth_sum=depth_sum)
+        return NUTSState(pos, logp, grad), NUTSWarmupInfo(step_avg, pooled_step_size(step_avg, eng.n_valid), acc_sum / num_steps, leap, n_div,
+                                                          depth_sum.double() / num_steps, traj)
+
     kernel.run = run
+    kernel.warmup = warmup
     return kernel
 
 
@@ -118,5 +164,10 @@ class nuts:
         def run_fn(rng_key, state, num_steps, thin=0):
             return kernel.run(rng_key, state, logdensity_fn, step_size, num_steps, thin, max_num_doublings, minv, divergence_threshold)
 
+        def warmup_fn(rng_key, state, num_steps, target_acceptance_rate=0.8, return_step_sizes=False):
+            return kernel.warmup(rng_key, state, logdensity_fn, step_size, num_steps, target_acceptance_rate, return_step_sizes, max_num_doublings,
+                                 minv, divergence_threshold)
+
         step_fn.run = run_fn
+        step_fn.warmup = warmup_fn
         return SamplingAlgorithm(init_fn, step_fn)

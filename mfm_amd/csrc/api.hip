@@ -18,6 +18,7 @@
 #include "hmc_run.hip"
 #include "nuts.hip"
 #include "warmup.hip"
+#include "nuts_warmup.hip.h"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -939,6 +940,44 @@ extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k
   x->ctr[CTR_MALA] += (int64_t)B * n_steps;
   x->ctr[CTR_MALA_BYTES] += (int64_t)B * 4 * (4 * d + 4) + (int64_t)B * 8 * (1 + (d_step_last ? 1 : 0) + (d_step_traj ? n_steps : 0));
   return MFM_OK;
+}
+
+// The NUTS warmup (nuts_warmup.hip.h): the warmup's checks, then the tree's own (nuts_args); a rejected call touches nothing.
+// window: mfm_nuts_warmup_window, which always runs the mass instances (the context's vector, or ones) and takes the window's sums
+static int nuts_warmup_common(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0,
+                              int32_t max_tree_depth, double div_thr, int32_t n_steps, double target_accept, float* d_pos, double* d_logp,
+                              float* d_grad, double* d_step_avg, double* d_step_last, double* d_acc_sum, double* d_step_traj, int64_t* d_tot_leap,
+                              int32_t* d_n_div, int32_t* d_depth_sum, bool window, double* d_pos_sum, double* d_pos_sumsq) {
+  CHECKED(warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg));
+  if (window && (!d_pos_sum || !d_pos_sumsq)) return fail(MFM_EINVAL, "d_pos_sum and d_pos_sumsq must not be null");
+  NutsRunArgs r; memset(&r, 0, sizeof r);
+  CHECKED(nuts_args(x, r.n, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, max_tree_depth, div_thr, d_pos, d_logp, d_grad, nullptr, nullptr,
+                    nullptr, nullptr, nullptr, nullptr));
+  if (window && !x->d_inv_mass) CHECKED(inv_mass_upload(x, std::vector<double>((size_t)x->cfg.dim, 1.0)));
+  if (window) r.n.h.minv = x->d_inv_mass;
+  r.t = RunTail{key_mode, n_steps, 0, nullptr, d_acc_sum, nullptr, nullptr};      // (a warmup keeps no trajectory; a transition has no accept / reject)
+  r.tot_leap = d_tot_leap; r.tot_div = d_n_div; r.tot_depth = d_depth_sum;
+  const WarmupArgs w{target_accept, d_step_avg, d_step_last, d_step_traj, window ? d_pos_sum : nullptr, window ? d_pos_sumsq : nullptr};
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_nuts_warmup(r, w, x->stream)) return too_large(x, "NUTS");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_nuts_run)
+  return MFM_OK;
+}
+extern "C" int mfm_nuts_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0,
+                               int32_t max_tree_depth, double div_thr, int32_t n_steps, double target_accept, float* d_pos, double* d_logp,
+                               float* d_grad, double* d_step_avg, double* d_step_last, double* d_acc_sum, double* d_step_traj,
+                               int64_t* d_tot_leap, int32_t* d_n_div, int32_t* d_depth_sum) { use_ctx(x);
+  return nuts_warmup_common(x, key_mode, k0, k1, d_keys, beta, step0, max_tree_depth, div_thr, n_steps, target_accept, d_pos, d_logp, d_grad,
+                            d_step_avg, d_step_last, d_acc_sum, d_step_traj, d_tot_leap, d_n_div, d_depth_sum, false, nullptr, nullptr);
+}
+extern "C" int mfm_nuts_warmup_window(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0,
+                                      int32_t max_tree_depth, double div_thr, int32_t n_steps, double target_accept, float* d_pos,
+                                      double* d_logp, float* d_grad, double* d_step_avg, double* d_step_last, double* d_acc_sum,
+                                      double* d_step_traj, int64_t* d_tot_leap, int32_t* d_n_div, int32_t* d_depth_sum, double* d_pos_sum,
+                                      double* d_pos_sumsq) { use_ctx(x);
+  return nuts_warmup_common(x, key_mode, k0, k1, d_keys, beta, step0, max_tree_depth, div_thr, n_steps, target_accept, d_pos, d_logp, d_grad,
+                            d_step_avg, d_step_last, d_acc_sum, d_step_traj, d_tot_leap, d_n_div, d_depth_sum, true, d_pos_sum, d_pos_sumsq);
 }
 
 extern "C" int mfm_loglik(mfm_ctx* x, const float* d_pos, double* d_out) { use_ctx(x);

@@ -355,28 +355,33 @@ static inline int nuts_waves(int d, int max_depth) {
 // the largest max_tree_depth at which one chain fits
 static inline int nuts_depth_that_fits(int d) { return 1 + (int)((NUTS_LDS_CU - mala_smem(d)) / (2 * (size_t)d * sizeof(double))); }
 
-#define NUTS_LAUNCH_(KERN, MAXIT, ARG)                                                                                  \
+// TAIL: what follows MASS in the kernel's template arguments -- `none` for the step and run kernels, `sums` / `nosums` for the SUMS flag
+// of nuts_warmup_kernel (nuts_warmup.hip.h)
+#define NUTS_TAIL_none
+#define NUTS_TAIL_sums , true
+#define NUTS_TAIL_nosums , false
+#define NUTS_LAUNCH_(KERN, MAXIT, TAIL, ...)                                                                            \
   do {                                                                                                                  \
     auto go = [&](auto kern) {                                                                                          \
       (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm);                \
-      hipLaunchKernelGGL(kern, grid, block, sm, stream, ARG);                                                           \
+      hipLaunchKernelGGL(kern, grid, block, sm, stream, __VA_ARGS__);                                                   \
     };                                                                                                                  \
-    if (mass) { if (bcrt) go(KERN<MAXIT, true, true>); else go(KERN<MAXIT, false, true>); }                             \
-    else { if (bcrt) go(KERN<MAXIT, true, false>); else go(KERN<MAXIT, false, false>); }                                \
+    if (mass) { if (bcrt) go(KERN<MAXIT, true, true NUTS_TAIL_##TAIL>); else go(KERN<MAXIT, false, true NUTS_TAIL_##TAIL>); }      \
+    else { if (bcrt) go(KERN<MAXIT, true, false NUTS_TAIL_##TAIL>); else go(KERN<MAXIT, false, false NUTS_TAIL_##TAIL>); }         \
   } while (0)
-// the instance KERN<MAXIT, BCRT, MASS> for the dimension, the phi-four boundary and the installed mass (n: the call's NutsArgs)
-#define NUTS_DISPATCH(KERN, ARG)                                                                 \
+// the instance KERN<MAXIT, BCRT, MASS, TAIL> for the dimension, the phi-four boundary and the installed mass (n: the call's NutsArgs)
+#define NUTS_DISPATCH(KERN, TAIL, ...)                                                           \
   do {                                                                                           \
     const int nit = (n.h.T.dim + 63) / 64;                                                       \
     const dim3 grid((n.h.B + n.waves - 1) / n.waves), block(n.waves * 64);                       \
     const size_t sm = nuts_smem(n.h.T.dim, n.max_depth, n.waves);                                \
     const bool bcrt = n.h.T.kind == MFM_TARGET_PHI4 && !phi4_default_bc(n.h.T);                  \
     const bool mass = n.h.minv != nullptr;                                                       \
-    if (nit <= 1) NUTS_LAUNCH_(KERN, 1, ARG);                                                    \
-    else if (nit <= 2) NUTS_LAUNCH_(KERN, 2, ARG);                                               \
-    else if (nit <= 4) NUTS_LAUNCH_(KERN, 4, ARG);                                               \
+    if (nit <= 1) NUTS_LAUNCH_(KERN, 1, TAIL, __VA_ARGS__);                                      \
+    else if (nit <= 2) NUTS_LAUNCH_(KERN, 2, TAIL, __VA_ARGS__);                                 \
+    else if (nit <= 4) NUTS_LAUNCH_(KERN, 4, TAIL, __VA_ARGS__);                                 \
     else return -2;                                                                              \
   } while (0)
 
-int launch_nuts_step(const NutsArgs& n, hipStream_t stream) { NUTS_DISPATCH(nuts_step_kernel, n); return 0; }
-int launch_nuts_run(const NutsRunArgs& r, hipStream_t stream) { const NutsArgs& n = r.n; NUTS_DISPATCH(nuts_run_kernel, r); return 0; }
+int launch_nuts_step(const NutsArgs& n, hipStream_t stream) { NUTS_DISPATCH(nuts_step_kernel, none, n); return 0; }
+int launch_nuts_run(const NutsRunArgs& r, hipStream_t stream) { const NutsArgs& n = r.n; NUTS_DISPATCH(nuts_run_kernel, none, r); return 0; }

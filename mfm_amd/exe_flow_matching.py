@@ -369,6 +369,8 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
     if adapt_stats:
         logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']} (mean acceptance probability over the warmup= {adapt_stats['adapt_acceptance']})")
+        if "adapt_mean_leapfrog" in adapt_stats:                                            # (--nuts_adapt tree)
+            logger.info(f"NUTS warmup: mean leapfrog steps per transition= {adapt_stats['adapt_mean_leapfrog']:.4g}")
         if "adapted_inverse_mass" in adapt_stats:
             logger.info(f"Adapted inverse mass matrix (diagonal): min= {adapt_stats['adapted_inverse_mass_min']}, max= {adapt_stats['adapted_inverse_mass_max']}")
         wandb.log({k: v for k, v in adapt_stats.items() if k != "adapted_inverse_mass"})
@@ -480,7 +482,8 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
 
 
 def check_adapt_args(args):
-    """``--adapt_steps`` needs ``--mcmc_kernel hmc`` (or ``nuts``, which runs the HMC warmup) and a run that takes MCMC steps: raised before any device work."""
+    """``--adapt_steps`` needs ``--mcmc_kernel hmc`` (or ``nuts``, which runs the HMC warmup, or with ``--nuts_adapt tree`` its own) and a run
+    that takes MCMC steps; ``--nuts_adapt tree`` needs ``--mcmc_kernel nuts``: raised before any device work."""
     n_steps = int(getattr(args, "adapt_steps", 0) or 0)
     if n_steps < 0:
         raise ValueError(f"--adapt_steps must not be negative (got {n_steps})")
@@ -491,6 +494,11 @@ def check_adapt_args(args):
     if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") not in ("hmc", "nuts"):
         raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
                          "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
+    nuts_adapt = getattr(args, "nuts_adapt", "hmc")
+    if nuts_adapt not in ("hmc", "tree"):
+        raise ValueError(f"--nuts_adapt must be hmc or tree (got {nuts_adapt!r})")
+    if nuts_adapt == "tree" and getattr(args, "mcmc_kernel", "mala") != "nuts":
+        raise ValueError("--nuts_adapt tree adapts on the No-U-turn sampler's own trees: it needs --mcmc_kernel nuts")
     return n_steps
 
 
@@ -509,12 +517,35 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     above (``adapt_acceptance``: of the last segment) the result carries ``adapted_inverse_mass`` (the vector) and its ``_min`` / ``_max``.
 
     ``--mcmc_kernel nuts``: the same HMC warmup with ``--hmc_steps`` leapfrog steps, whose step size and mass NUTS then samples with -- the
-    integrator and the metric are the same; it approximates adapting on the tree's own acceptance statistic."""
+    integrator and the metric are the same; it approximates adapting on the tree's own acceptance statistic.  With ``--nuts_adapt tree``
+    the warmup is NUTS's own instead: N transitions under ``--max_tree_depth`` in one launch (``nuts(...).step.warmup``,
+    ``mfm_nuts_warmup``), every chain adapting on the mean over its tree's leaves of ``min(1, exp(H0 - H))``; with ``--adapt_mass``
+    ``nuts_window_adaptation``.  ``--hmc_steps`` plays no part, and the result also carries ``adapt_mean_leapfrog``, the mean number
+    of leapfrog steps per transition over the warmup (with ``--adapt_mass``: of the last segment)."""
     n_steps = check_adapt_args(args)
     if n_steps <= 0:
         return {}
     from .bblackjax.mcmc.hmc import hmc
     from .engine import global_mean_std
+    if getattr(args, "nuts_adapt", "hmc") == "tree":
+        from .bblackjax.mcmc.nuts import nuts
+        depth, target = int(getattr(args, "max_tree_depth", 10)), float(getattr(args, "adapt_target", 0.8))
+        algo = nuts(dist.logprob, args.step_size, depth)
+        if getattr(args, "adapt_mass", False):
+            from .bblackjax.adaptation.window_adaptation import nuts_window_adaptation
+            wa = nuts_window_adaptation(dist.logprob, depth, args.step_size, target)
+            _, params, info = wa.run(jr.split(key_gen, 4)[3], algo.init(pos0), n_steps)
+            minv = params["inverse_mass_matrix"]
+            args.step_size, args.inverse_mass_matrix = params["step_size"], minv
+            eng.ctx.set_inverse_mass(minv)
+            return dict(adapted_step_size=params["step_size"], adapt_acceptance=info.acceptance_rates[-1],
+                        adapt_mean_leapfrog=info.mean_integration_steps[-1], adapted_inverse_mass=minv,
+                        adapted_inverse_mass_min=float(minv.min()), adapted_inverse_mass_max=float(minv.max()))
+        _, info = algo.step.warmup(jr.split(key_gen, 4)[3], algo.init(pos0), n_steps, target)
+        args.step_size = info.pooled_step_size
+        acc, _ = global_mean_std(info.acceptance_rate[:eng.n_valid], eng.n_total)
+        leap, _ = global_mean_std(info.num_integration_steps[:eng.n_valid].double() / n_steps, eng.n_total)
+        return dict(adapted_step_size=info.pooled_step_size, adapt_acceptance=acc.item(), adapt_mean_leapfrog=leap.item())
     if getattr(args, "adapt_mass", False):
         from .bblackjax.adaptation.window_adaptation import window_adaptation
         algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps))

@@ -4,7 +4,7 @@ overrides, ``multi_modal.py:21-101,147-220``), running the MFM loop on MI355X.
 Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / ``--force_num_chain`` override the
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
-``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows),
+``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic),
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -177,6 +177,9 @@ def build_parser():
     # with --adapt_steps N: the N steps run the window adaptation (bblackjax/adaptation/window_adaptation.py) instead of the single warmup --
     # step size AND a diagonal mass matrix, which the training loop's HMC steps and --ess_steps then use
     parser.add_argument('--adapt_mass', action='store_true')
+    # with --mcmc_kernel nuts --adapt_steps N: 'hmc' runs the HMC warmup with --hmc_steps leapfrog steps and hands its step size (and mass) to
+    # NUTS; 'tree' runs NUTS's own warmup under --max_tree_depth, adapting on the trees' acceptance statistic (--hmc_steps plays no part)
+    parser.add_argument('--nuts_adapt', type=str, default='hmc', choices=['hmc', 'tree'])
     return parser
 
 
