@@ -214,6 +214,11 @@ int mfm_nuts_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const
                  int32_t* d_depth, int32_t* d_num_leapfrog, uint8_t* d_is_turning, uint8_t* d_is_divergent,
                  double* d_acceptance_rate, double* d_energy,
                  float* d_traj_pos, double* d_traj_logp);
+/* The launch geometry of the NUTS kernels (step, run and warmup) at (dim, max_tree_depth); needs no context and no GPU.  *h_waves: the
+ * chains per workgroup (1 .. 4), the count that puts the most chains on a CU, the larger count on a tie; *h_lds_bytes: the dynamic LDS of
+ * one workgroup, the MALA rows and gradient scratch followed by h_waves checkpoint slabs of (max_tree_depth - 1) * 2 * dim doubles;
+ * *h_workgroups_per_cu: how many such workgroups a CU's 163840 B hold.  Errors as mfm_nuts_step's for max_tree_depth and dim. */
+int mfm_nuts_launch_plan(int32_t dim, int32_t max_tree_depth, int32_t* h_waves, int32_t* h_lds_bytes, int32_t* h_workgroups_per_cu);
 /* STEP-SIZE WARMUP: n_steps steps of the HMC step (mfm_hmc_warmup) or of the MALA step under the textbook rule (mfm_mala_warmup) in
  * ONE launch, as mfm_hmc_run / mfm_mala_run (chain resident in registers, key_mode 0 / 1 and their key schedules), in which every
  * chain adapts its OWN step size by Nesterov dual averaging on its acceptance probability (Hoffman & Gelman 2014, algorithm 5).

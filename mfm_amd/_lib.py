@@ -121,6 +121,7 @@ _SIGS = {
     "mfm_fm_eval_instance": (C.c_int, [_P, C.c_int]),
     "mfm_threefry2x32": (C.c_int, [_U32, _U32, _U32, _U32, C.POINTER(_U32)]),
     "mfm_wsk_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mfm_nuts_launch_plan": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mfm_wgrad_info": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "mfm_wide_gemm_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(C.c_int32)]),
     "mfm_wide_gemm_tally": (C.c_int, [_P, C.POINTER(C.c_int64), C.c_int]),
@@ -186,7 +187,14 @@ def wsk_plan(n_jobs, nbb, cap, g_override=0, ranges=True):
     return plan
 
 
-WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2      # mfm_wgrad_info: kind
+def nuts_launch_plan(dim, max_tree_depth):
+    """``mfm_nuts_launch_plan`` (host only): ``(chains per workgroup, LDS bytes per workgroup, workgroups per CU)`` of the NUTS kernels."""
+    w, sm, per_cu = C.c_int32(), C.c_int32(), C.c_int32()
+    _chk(load().mfm_nuts_launch_plan(int(dim), int(max_tree_depth), C.byref(w), C.byref(sm), C.byref(per_cu)))
+    return w.value, sm.value, per_cu.value
+
+
+WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2     # mfm_wgrad_info: kind
 
 # include/mfm.h: MFM_WGEMM_* (the instances of the wide family's GEMM, in enum order) and MFM_WGEMM_SW_* (its latched switches)
 WGEMM = ("11", "11_dual", "12", "12_dual", "22", "22_dual", "22_ring8", "22_ring8_dual", "big", "lds", "lds_dual", "lds_wm1", "lds_wm1_dual")

@@ -814,16 +814,26 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
 }
 
 // The No-U-turn sampler (nuts.hip).  Checks in mfm_hmc_run's order, then the tree's own: a rejected call touches nothing.
+static int nuts_check_depth(int32_t max_tree_depth) {
+  if (max_tree_depth < 1 || max_tree_depth > NUTS_MAX_DEPTH) return fail(MFM_EINVAL, "max_tree_depth must be in [1, %d] (got %d)", NUTS_MAX_DEPTH, max_tree_depth);
+  return MFM_OK;
+}
+// the chains per workgroup of a launch at (dim, max_tree_depth): nuts_args' and mfm_nuts_launch_plan's
+static int nuts_geometry(int d, int32_t max_tree_depth, int& waves) {
+  if (d > NUTS_MAX_DIM) return fail(MFM_EUNSUPPORTED, "the NUTS step serves dim <= %d (got %d): the larger instances need the tree's checkpoints outside LDS", NUTS_MAX_DIM, d);
+  waves = nuts_waves(d, max_tree_depth);
+  if (waves < 1) return fail(MFM_EINVAL, "max_tree_depth %d needs more LDS than a CU has at dim %d: the largest depth that fits is %d", max_tree_depth, d, nuts_depth_that_fits(d));
+  return MFM_OK;
+}
 static int nuts_args(mfm_ctx* x, NutsArgs& n, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t max_tree_depth,
                      double div_thr, float* d_pos, double* d_logp, float* d_grad, int32_t* d_depth, int32_t* d_nleap, uint8_t* d_turn, uint8_t* d_div,
                      double* d_rate, double* d_energy) {
-  if (max_tree_depth < 1 || max_tree_depth > NUTS_MAX_DEPTH) return fail(MFM_EINVAL, "max_tree_depth must be in [1, %d] (got %d)", NUTS_MAX_DEPTH, max_tree_depth);
+  CHECKED(nuts_check_depth(max_tree_depth));
   if (!(div_thr > 0)) return fail(MFM_EINVAL, "divergence_threshold must be positive (got %g)", div_thr);
   if (x->net.T.kind == MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "the NUTS step serves the phi-four and mixture targets (the Cox process needs the K^-1 GEMM tile)");
   const int d = x->cfg.dim;
-  if (d > NUTS_MAX_DIM) return fail(MFM_EUNSUPPORTED, "the NUTS step serves dim <= %d (got %d): the larger instances need the tree's checkpoints outside LDS", NUTS_MAX_DIM, d);
-  const int waves = nuts_waves(d, max_tree_depth);
-  if (waves < 1) return fail(MFM_EINVAL, "max_tree_depth %d needs more LDS than a CU has at dim %d: the largest depth that fits is %d", max_tree_depth, d, nuts_depth_that_fits(d));
+  int waves = 0;
+  CHECKED(nuts_geometry(d, max_tree_depth, waves));
   memset(&n, 0, sizeof n);
   n.h = hmc_args(x, k0, k1, d_keys, beta, step, 0, d_pos, d_logp, d_grad, nullptr, nullptr);
   n.max_depth = max_tree_depth; n.waves = waves; n.div_thr = div_thr;
@@ -1169,6 +1179,16 @@ extern "C" int mfm_wsk_plan(int n_jobs, int nbb, int cap, int g_override, int32_
     wsk_ranges(n_jobs, nbb, G, q, r, nullptr, wg.data());
     for (int w = 0; w < G; ++w) { h_wg[4 * w] = wg[w].j0; h_wg[4 * w + 1] = wg[w].bb0; h_wg[4 * w + 2] = wg[w].cnt; h_wg[4 * w + 3] = wg[w].n0; }
   }
+  return MFM_OK;
+}
+extern "C" int mfm_nuts_launch_plan(int32_t dim, int32_t max_tree_depth, int32_t* h_waves, int32_t* h_lds_bytes, int32_t* h_workgroups_per_cu) {
+  if (!h_waves || !h_lds_bytes || !h_workgroups_per_cu) return fail(MFM_EINVAL, "mfm_nuts_launch_plan: null output pointer");
+  if (dim < 1) return fail(MFM_EINVAL, "mfm_nuts_launch_plan: dim must be positive (got %d)", dim);
+  CHECKED(nuts_check_depth(max_tree_depth));
+  int waves = 0;
+  CHECKED(nuts_geometry(dim, max_tree_depth, waves));
+  const size_t sm = nuts_smem(dim, max_tree_depth, waves);
+  *h_waves = waves; *h_lds_bytes = (int32_t)sm; *h_workgroups_per_cu = (int32_t)(NUTS_LDS_CU / sm);
   return MFM_OK;
 }
 extern "C" int mfm_wgrad_info(mfm_ctx* x, int32_t h_out[6]) { use_ctx(x);

@@ -19,18 +19,20 @@ Step sizes and burn-in (``max_tree_depth`` 6): phi-four 0.03 at d <= 64 and 0.02
 transitions of the reference itself from the initial draw, where |logp| is 4e3 (d = 64) to 5e4 (d = 256) and ``tol_e`` would swallow
 every decision; after them it is 50 to 200.  Reference alone, unit mass: at d <= 64 two thirds of the trees end on a U-turn at depths 3 to
 6 and the borderline shares are 0.02 to 0.16; at d = 256 the slow modes outlast 63 steps of 0.02, nearly every tree is cut by the limit
-and the shares are 0.14 to 0.17; the mixtures' trees have depths 1 to 5 and shares under 0.08."""
-import functools
+and the shares are 0.14 to 0.17; the mixtures' trees have depths 1 to 5 and shares under 0.08.
 
+The helpers (setup, burn-in, the borderline rule, the comparison) live in tests/nuts_util.py, shared with
+tests/test_gpu_nuts_instances.py, which runs the same comparison on every kernel instance and launch geometry."""
 import numpy as np
 import pytest
 
 from oracle import mala as omala, prng, targets
-from tests import hmc_mass_ref as hm, nuts_ref as nr
+from tests import nuts_ref as nr, nuts_util as nu
+from tests.nuts_util import (B, BURN, DEPTH, INFO, N_TRANS, _borderline, _compare, _ctx, _dev_info, _init, _keys_dev, _ref_state,      # noqa: F401
+                             _run, _setup, _stepwise, _tol_e)      # (re-exported: tests/test_gpu_nuts_warmup.py takes them from here)
 
 pytestmark = pytest.mark.gpu
 
-B, DEPTH, BURN, N_TRANS = 64, 6, 30, 3
 # name: (target, d, phi-four block tail or None, step size)
 CASES = {
     "phi4-64": ("phi4", 64, None, 0.03),
@@ -40,108 +42,14 @@ CASES = {
     "gmm4": ("gmm4", 2, None, 0.3),
     "gmm16": ("gmm16", 2, None, 0.15),
 }
-INFO = ("depth", "num_leapfrog", "is_turning", "is_divergent", "acceptance_rate", "energy")
 
 
-def _setup(kind, d, tail, n=B):
-    """The oracle's arguments and target for a case (the periodic ring: tests/phi4_bc_oracle.py)."""
-    from tests import gpu_util as gu
-    if kind == "phi4":
-        args, dist, *_ = gu.phi4_setup(d=d, B=n, hidden=32, F=16)
-        if tail is not None:
-            from tests.phi4_bc_oracle import PhiFourBC
-            bc = PhiFourBC(d, dist.a, dist.beta, ("pbc", 0.0))
-            bc.init_params = dist.init_params
-            return args, dist, bc
-        return args, dist, dist
-    args, dist, *_ = gu.gmm4_setup(B=n) if kind == "gmm4" else gu.gmm16_setup(B=n, hidden=32, F=16)
-    return args, dist, dist
-
-
-def _ctx(kind, d, tail, n=B):
-    import torch
-    from mfm_amd import _lib
-    from tests import gpu_util as gu
-    args, dist, odist = _setup(kind, d, tail, n)
-    ctx = gu.make_ctx(dist, args)
-    if tail is not None:
-        ctx.set_target(_lib.PHI4, [dist.a, dist.beta] + tail)
-    return ctx, torch.as_tensor(dist.init_params.astype(np.float32)).cuda(), odist
-
-
-def _tol_e(kind, logp):
-    return 5e-6 * max(1.0, np.abs(logp).max()) + (5e-4 if kind.startswith("gmm") else 0.0)
-
-
-def _borderline(kind, logp, info):
-    t = 10 * _tol_e(kind, logp)
-    return (info.margin_draw < t) | (info.margin_div < t) | (info.margin_turn < 1e-4)
-
-
-def _ref_state(vg, x32):
-    lp, g = vg(x32.astype(np.float64))
-    return omala.MALAState(x32.astype(np.float64), lp, g.astype(np.float32).astype(np.float64))
-
-
-@functools.lru_cache(maxsize=None)
 def _burned(case, mass):
     """The case's start: the reference's own state after BURN transitions from the initial draw, and the reference-only pass of
-    N_TRANS transitions from it with the share of borderline chains in each."""
+    N_TRANS transitions from it with the share of borderline chains in each (tests/nuts_util.py: computed once)."""
     kind, d, tail, eps = CASES[case]
-    _, dist, odist = _setup(kind, d, tail)
-    vg = targets.Tempered(odist, 1.0).value_and_grad
-    minv = hm.log_spaced_mass(d) if mass else None
-    st = _ref_state(vg, dist.init_params.astype(np.float32))
-    for it in range(BURN):
-        st, _ = nr.kernel(prng.split(prng.PRNGKey(900 + it), B), st, vg, eps, DEPTH, inverse_mass=minv)
-    start = st.position.astype(np.float32)
-    shares, infos = [], []
-    for it in range(N_TRANS):
-        st_n, info = nr.kernel(prng.split(prng.PRNGKey(50 + it), B), st, vg, eps, DEPTH, inverse_mass=minv)
-        shares.append(_borderline(kind, st.logdensity, info).mean())
-        infos.append(info)
-        st = st_n
-    return start, minv, shares, infos
-
-
-def _dev_info(n):
-    import torch
-    return dict(depth=torch.empty(n, dtype=torch.int32, device="cuda"), num_leapfrog=torch.empty(n, dtype=torch.int32, device="cuda"),
-                is_turning=torch.empty(n, dtype=torch.uint8, device="cuda"), is_divergent=torch.empty(n, dtype=torch.uint8, device="cuda"),
-                acceptance_rate=torch.empty(n, dtype=torch.float64, device="cuda"), energy=torch.empty(n, dtype=torch.float64, device="cuda"))
-
-
-def _init(ctx, pos0):
-    import torch
-    pos = pos0.clone()
-    logp = torch.empty(pos.shape[0], dtype=torch.float64, device="cuda"); grad = torch.empty_like(pos)
-    ctx.mala_init(pos, 1.0, logp, grad)
-    return pos, logp, grad
-
-
-def _keys_dev(keys):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(keys, dtype=np.uint32).view(np.int32)).cuda()
-
-
-def _compare(kind, st, info, state_g, info_g, ok, what):
-    """The kernel's transition against the reference's on the chains ``ok``."""
-    pos_g, logp_g = state_g[0].cpu().numpy().astype(np.float64), state_g[1].cpu().numpy()
-    g = {k: v.cpu().numpy() for k, v in info_g.items()}
-    tol = _tol_e(kind, st.logdensity)
-    print(f"{what}: {ok.sum()} of {ok.size} chains compared; depths {np.bincount(info.depth)}; leapfrog mean {info.num_leapfrog.mean():.1f}; "
-          f"turning {info.is_turning.sum()} divergent {info.is_divergent.sum()} stopped in a subtree {info.stopped_in_subtree.sum()}; "
-          f"max |pos diff| {np.abs(pos_g - st.position)[ok].max():.2e} max |logp diff| {np.abs(logp_g - st.logdensity)[ok].max():.2e} "
-          f"max |rate diff| {np.abs(g['acceptance_rate'] - info.acceptance_rate)[ok].max():.2e} tol_e {tol:.2e}")
-    np.testing.assert_array_equal(g["depth"][ok], info.depth[ok], err_msg=what)
-    np.testing.assert_array_equal(g["num_leapfrog"][ok], info.num_leapfrog[ok], err_msg=what)
-    np.testing.assert_array_equal(g["is_turning"][ok].astype(bool), info.is_turning[ok], err_msg=what)
-    np.testing.assert_array_equal(g["is_divergent"][ok].astype(bool), info.is_divergent[ok], err_msg=what)
-    assert np.abs(pos_g - st.position)[ok].max() < 3e-6 * max(1.0, np.abs(st.position).max()), what
-    lp_tol = 2e-6 * max(1.0, np.abs(st.logdensity).max()) + (5e-4 if kind.startswith("gmm") else 0.0)
-    assert np.abs(logp_g - st.logdensity)[ok].max() < lp_tol, what
-    assert np.abs(g["acceptance_rate"] - info.acceptance_rate)[ok].max() < tol, what
-    assert np.abs(g["energy"] - info.energy)[ok].max() < tol + lp_tol, what
+    r = nu.burned(kind, d, None if tail is None else tuple(tail), eps, DEPTH, mass)
+    return r["start"], r["minv"], r["shares"], r["infos"]
 
 
 @pytest.mark.parametrize("mass", [False, True], ids=["unit", "mass"])
@@ -155,59 +63,19 @@ def test_transitions_match_the_reference(case, mass):
         assert max(i.depth.max() for i in infos) >= 4
         assert any((i.directions > 0).any() for i in infos) and any((i.directions < 0).any() for i in infos)
         assert any(i.stopped_in_subtree.any() for i in infos)
-    import torch
-    ctx, _, odist = _ctx(kind, d, tail)
-    ctx.set_inverse_mass(minv)
-    vg = targets.Tempered(odist, 1.0).value_and_grad
-    pos, logp, grad = _init(ctx, torch.as_tensor(start).cuda())
-    buf = _dev_info(B)
-    st = omala.MALAState(pos.cpu().numpy().astype(np.float64), logp.cpu().numpy(), grad.cpu().numpy().astype(np.float64))
-    for it in range(N_TRANS):
-        key = prng.PRNGKey(50 + it)
-        ctx.nuts_step(key, 1.0, eps, DEPTH, pos, logp, grad, **buf)
-        st_o, info = nr.kernel(prng.split(key, B), st, vg, eps, DEPTH, inverse_mass=minv)
-        border = _borderline(kind, st.logdensity, info)
-        assert border.mean() <= 0.25, (it, border.mean())
-        _compare(kind, st_o, info, (pos, logp), buf, ~border, f"{case} mass={mass} transition {it}")
-        # both sides continue from the KERNEL's state (a borderline tree must not cascade)
-        st = omala.MALAState(pos.cpu().numpy().astype(np.float64), logp.cpu().numpy(), grad.cpu().numpy().astype(np.float64))
-    ctx.close()
+    # N_TRANS transitions of nuts_step on keys 50 + it against nr.kernel over the non-borderline chains, each with its own share
+    # asserted <= 0.25, both sides continued from the kernel's state (tests/nuts_util.py)
+    nu._transitions_against_the_reference(kind, d, tail, eps, DEPTH, minv, start, f"{case} mass={mass}")
 
 
 # ---- device only ------------------------------------------------------------------------------------------------------------
-BITS = {"phi4-64": ("phi4", 64, None, 0.03), "phi4-100": ("phi4", 100, None, 0.03), "phi4-256": ("phi4", 256, None, 0.02),
-        "phi4-64-pbc": ("phi4", 64, [1.0, 0.0], 0.03), "gmm4": ("gmm4", 2, None, 0.3)}
+# name: (target, d, phi-four block tail or None, step size, max_tree_depth); the chains per workgroup at the deep limits are 1 (d = 64
+# at 12, d = 128 at 14) and 2 (d = 256 at 14), asserted through the launch plan in tests/test_nuts_cases.py
+BITS = {"phi4-64": ("phi4", 64, None, 0.03, 5), "phi4-100": ("phi4", 100, None, 0.03, 5), "phi4-256": ("phi4", 256, None, 0.02, 5),
+        "phi4-64-pbc": ("phi4", 64, [1.0, 0.0], 0.03, 5), "gmm4": ("gmm4", 2, None, 0.3, 5),
+        "phi4-64-limit12": ("phi4", 64, None, 0.03, 12), "phi4-128-limit14": ("phi4", 128, None, 0.03, 14),
+        "phi4-256-limit14": ("phi4", 256, None, 0.02, 14)}
 N_RUN, NB = 4, 16
-
-
-def _stepwise(ctx, state0, key, eps, n_steps, depth):
-    from mfm_amd import random as jr
-    pos, logp, grad = (t.clone() for t in state0)
-    buf = _dev_info(pos.shape[0])
-    per_chain = np.ndim(key) == 2
-    step_keys = jr.split_rows(key, n_steps) if per_chain else jr.split(key, n_steps)
-    out = {k: [] for k in ("pos", "logp", "grad") + INFO}
-    for j in range(n_steps):
-        if per_chain:
-            ctx.nuts_step_keys(_keys_dev(step_keys[:, j]), 1.0, eps, depth, pos, logp, grad, **buf)
-        else:
-            ctx.nuts_step(step_keys[j], 1.0, eps, depth, pos, logp, grad, **buf)
-        for name, t in zip(out, (pos, logp, grad) + tuple(buf[k] for k in INFO)):
-            out[name].append(t.cpu().numpy().copy())
-    return {k: np.stack(v) for k, v in out.items()}
-
-
-def _run(ctx, state0, key, eps, n_steps, depth, thin=1):
-    import torch
-    pos, logp, grad = (t.clone() for t in state0)
-    n, d = pos.shape
-    buf = _dev_info(n)
-    tot = dict(leapfrog_sum=torch.empty(n, dtype=torch.int64, device="cuda"), acc_sum=torch.empty(n, dtype=torch.float64, device="cuda"),
-               n_divergent=torch.empty(n, dtype=torch.int32, device="cuda"), depth_sum=torch.empty(n, dtype=torch.int32, device="cuda"))
-    tp = torch.empty(n_steps // thin, n, d, device="cuda"); tl = torch.empty(n_steps // thin, n, dtype=torch.float64, device="cuda")
-    ctx.nuts_run(_keys_dev(key) if np.ndim(key) == 2 else key, 1.0, eps, depth, n_steps, pos, logp, grad, thin=thin, traj_pos=tp, traj_logp=tl, **tot, **buf)
-    out = dict(pos=pos, logp=logp, grad=grad, traj_pos=tp, traj_logp=tl, **tot, **buf)
-    return {k: v.cpu().numpy() for k, v in out.items()}
 
 
 def _assert_run_equals_steps(run, steps):
@@ -228,25 +96,25 @@ def _assert_run_equals_steps(run, steps):
 def test_run_has_the_bits_of_the_single_steps(case):
     """``mfm_nuts_run`` over n steps against n launches of ``mfm_nuts_step`` on ``split(key, n)[j]`` and of ``mfm_nuts_step_keys`` on
     ``split(keys[b], n)[j]``: state, thinned trajectory, totals, last info; and a mass of ones against the unit instances."""
-    kind, d, tail, eps = BITS[case]
+    kind, d, tail, eps, limit = BITS[case]
     ctx, pos0, _ = _ctx(kind, d, tail, NB)
     state0 = _init(ctx, pos0)
     key, keys = prng.PRNGKey(21), prng.split(prng.PRNGKey(22), NB)
     unit = None
     for k in (key, keys):
-        steps = _stepwise(ctx, state0, k, eps, N_RUN, 5)
-        run = _run(ctx, state0, k, eps, N_RUN, 5)
+        steps = _stepwise(ctx, state0, k, eps, N_RUN, limit)
+        run = _run(ctx, state0, k, eps, N_RUN, limit)
         _assert_run_equals_steps(run, steps)
         assert len(set(steps["depth"].reshape(-1).tolist())) > 1 and (steps["pos"][-1] != state0[0].cpu().numpy()).any()
         unit = run if unit is None else unit
-    thinned = _run(ctx, state0, key, eps, N_RUN, 5, thin=2)
+    thinned = _run(ctx, state0, key, eps, N_RUN, limit, thin=2)
     np.testing.assert_array_equal(thinned["traj_pos"], unit["traj_pos"][1::2])
     np.testing.assert_array_equal(thinned["traj_logp"], unit["traj_logp"][1::2])
     ctx.set_inverse_mass(np.ones(d))
-    ones = _run(ctx, state0, key, eps, N_RUN, 5)
+    ones = _run(ctx, state0, key, eps, N_RUN, limit)
     for name in unit:
         np.testing.assert_array_equal(ones[name], unit[name], err_msg="mass of ones: " + name)
-    np.testing.assert_array_equal(_stepwise(ctx, state0, key, eps, N_RUN, 5)["pos"], unit["traj_pos"])      # (the step kernel's mass instances)
+    np.testing.assert_array_equal(_stepwise(ctx, state0, key, eps, N_RUN, limit)["pos"], unit["traj_pos"])      # (the step kernel's mass instances)
     ctx.close()
 
 

@@ -18,7 +18,9 @@ alone (tests/nuts_warmup_ref.py, on the CPU) meets both in every case but one --
 2 10 14 16, mass 1 1 1 1 1 2 8 14; phi4-256 unit 1 1 1 1 1 1 3 12; phi4-48 unit 1 1 1 1 15 16 16 16, mass 1 1 1 12 12 15 16 16;
 phi4-64-pbc unit 1 1 1 1 2 12 15 16, mass 1 1 1 1 1 2 7 13; gmm4 unit 1 7 7 8 13 16 16 16, mass 1 4 4 7 15 16 16 16; depths 0 to 6
 everywhere (gmm4 mass: 0 to 5).  phi4-256 under the mass has p of 1, 0, 0, 1, 1, 1 in every chain and parts at the eighth transition
-only (1 ... 1 2 7 12 15 16 over twelve), so that case runs 12 transitions."""
+only (1 ... 1 2 7 12 15 16 over twelve), so that case runs 12 transitions.  phi4-128-limit14 is the same replay at ``max_tree_depth``
+14, where the launch holds ONE chain per workgroup (tests/test_nuts_cases.py asserts it through ``mfm_nuts_launch_plan``); the step
+kernel at that geometry is held to the reference in tests/test_gpu_nuts_instances.py."""
 import numpy as np
 import pytest
 
@@ -111,21 +113,23 @@ def _assert_warmup_equals_replay(w, rep, step0, target=TARGET):
     return parted, len(np.unique(rep["depth"]))
 
 
-REPLAY_CASES = ["phi4-64", "phi4-256", "phi4-48", "phi4-64-pbc", "gmm4"]
+# name: (target, d, phi-four block tail or None, first step size, max_tree_depth); d = 128 at limit 14 runs one chain per workgroup
+REPLAY_CASES = {**{name: CASES[name] + (DEPTH,) for name in ("phi4-64", "phi4-256", "phi4-48", "phi4-64-pbc", "gmm4")},
+                "phi4-128-limit14": ("phi4", 128, None, 0.03, 14)}
 LONGER = {("phi4-256", True): 12}                                              # (module docstring)
 
 
 @pytest.mark.parametrize("mass", [False, True], ids=["unit", "mass"])
 @pytest.mark.parametrize("case", REPLAY_CASES)
 def test_warmup_replays_as_single_transitions_and_follows_the_recursion(case, mass):
-    kind, d, tail, step0 = CASES[case]
+    kind, d, tail, step0, limit = REPLAY_CASES[case]
     n_steps = LONGER.get((case, mass), N_STEPS)
     ctx, pos0, _ = _ctx(kind, d, tail, B)
     ctx.set_inverse_mass(hm.log_spaced_mass(d) if mass else None)
     state0 = _init(ctx, pos0)
     key = prng.PRNGKey(21)
-    w = _warmup(ctx, state0, key, step0, n_steps)
-    parted, n_depths = _assert_warmup_equals_replay(w, _replay(ctx, state0, key, w["step_traj"]), step0)
+    w = _warmup(ctx, state0, key, step0, n_steps, depth=limit)
+    parted, n_depths = _assert_warmup_equals_replay(w, _replay(ctx, state0, key, w["step_traj"], depth=limit), step0)
     assert parted and n_depths >= 3, (parted, n_depths)
     ctx.close()
 

@@ -180,7 +180,7 @@ def test_host_surface():
     assert N.NUTSInfo._fields == ("num_trajectory_expansions", "num_integration_steps", "is_turning", "is_divergent", "acceptance_rate", "energy")
     assert callable(N.build_kernel().run)
     hdr = open(os.path.join(ROOT, "include", "mfm.h")).read()
-    for name, nargs in (("mfm_nuts_step", 16), ("mfm_nuts_step_keys", 15), ("mfm_nuts_run", 26)):
+    for name, nargs in (("mfm_nuts_step", 16), ("mfm_nuts_step_keys", 15), ("mfm_nuts_run", 26), ("mfm_nuts_launch_plan", 5)):
         assert name in _lib.EXPORTS and len(_lib._SIGS[name][1]) == nargs
         decl = re.search(r"int %s\(([^;]*)\);" % name, hdr).group(1)
         assert len(re.sub(r"/\*.*?\*/", "", decl, flags=re.S).split(",")) == nargs, name

@@ -20,18 +20,11 @@ import numpy as np  # noqa: E402
 SHAPES = [("phi-four d=64, 4096 chains", 64, 4096, 0.03), ("phi-four d=256, 4096 chains", 256, 4096, 0.02)]
 
 
-def lds_budget(d, depth, cu=163840, max_waves=4):
-    """(chains per workgroup, workgroups per CU, LDS bytes per workgroup): nuts.hip's nuts_waves restated."""
-    fixed = (4 * (d + 2) + 4 * 8) * 4
-    per = (depth - 1) * 2 * d * 8
-    best = (0, 0, 0)
-    for w in range(1, max_waves + 1):
-        sm = fixed + w * per
-        if sm > cu:
-            break
-        if (cu // sm) * w >= best[0] * best[1]:
-            best = (w, cu // sm, sm)
-    return best
+def lds_budget(d, depth):
+    """(chains per workgroup, workgroups per CU, LDS bytes per workgroup): the library's own answer (mfm_nuts_launch_plan)."""
+    from mfm_amd import _lib
+    w, sm, per_cu = _lib.nuts_launch_plan(d, depth)
+    return w, per_cu, sm
 
 
 def _timed(fn, reset, reps):
