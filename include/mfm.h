@@ -510,6 +510,51 @@ int mfm_choice_logw(mfm_ctx* ctx, uint32_t key0, uint32_t key1, const double* d_
  * (exe_flow_matching.py:442-443: infos.acceptance_rate.mean() / .std()) without a host round trip */
 int mfm_acc_stats(mfm_ctx* ctx, const float* d_x, int n, double* d_out);
 
+/* ---- Stein variational gradient descent (bblackjax/vi/svgd.py, optimizers/cocob.py; svgd.hip) ------------------------------------
+ * Particles x_i (i < n, row-major [n][d] float32), g_i = grad log pi_beta(x_i), length scale h (ONE float64 on the device):
+ *   k_ij = exp(-(1/h) |x_i - x_j|^2)                                                        (svgd.py:94-96)
+ *   fg_i = -(1/n) sum_j [ k_ij g_j + (2/h) k_ij (x_i - x_j) ]                               (:74-84, the functional gradient)
+ *        = -(1/n) [ (K G)_i + (2/h) ( s_i x_i - (K X)_i ) ],   s_i = sum_j k_ij
+ *   x <- x + optimizer(fg)                                                                  (:86-87)
+ *   h <- median^2 / log(n), median over the n (n - 1) / 2 distances |x_i - x_j|, i > j, of the NEW particles; the mean of the two
+ *        middle values when their count is even                                              (:99-124, :164-166)
+ * Free shapes: any n in [2, 16384] (more: MFM_ETOOLARGE) and any d >= 1.  Deterministic (no float atomics), asynchronous on the
+ * context's stream, no host synchronisation; a rejected call touches nothing and its message names the argument.
+ *
+ * mfm_svgd_sqdist: d_D [n][n] float32, D_ij = |x_i - x_j|^2 by q_i + q_j - 2 xc_i . xc_j on the exact-f32 matrix pipe, xc = x - column
+ *   mean (the mean in float64); clamped at 0, diagonal exactly 0, symmetric to the bit;
+ *   |D_ij - exact| <= (d + 8) 2^-23 (q_i + q_j), q the centred squared norms.
+ * mfm_svgd_median: d_length_scale[0] = ((sqrt a + sqrt b) / 2)^2 / log n in float64, a <= b the two middle order statistics (equal for
+ *   an odd count) of the strict lower triangle of the float32 d_D, selected exactly.  All particles equal: 0.
+ * mfm_svgd_gradient: d_fg [n_rows][d] float32 = rows [i0, i0 + n_rows) of fg, from x, g [n][d], D [n][n] and *d_length_scale; the weights
+ *   exp(-D / h) are float32 and s_i sums the same weights the products use.  A row range has the bits of those rows of the full call.
+ * mfm_svgd_apply: x <- x + update(fg) on n x d elements in place, in float64 per element; `count` is the number of updates ALREADY
+ *   applied.  h_hyper[4] and the state arrays d_s0 .. d_s4 ([n][d] float32, NULL beyond the kind's) by kind:
+ *   MFM_SVGD_SGD     {learning_rate}: x -= lr fg.
+ *   MFM_SVGD_ADAGRAD {learning_rate, initial_accumulator_value, eps}, s0 = acc (created at the initial value):
+ *                    acc += fg^2; x -= lr fg / sqrt(acc + eps) where acc > 0 (optax 0.1.9's form).
+ *   MFM_SVGD_ADAM    {learning_rate, b1, b2, eps}, s0 = m, s1 = v: m = b1 m + (1 - b1) fg; v = b2 v + (1 - b2) fg^2; t = count + 1;
+ *                    x -= lr (m / (1 - b1^t)) / (sqrt(v / (1 - b2^t)) + eps).
+ *   MFM_SVGD_COCOB   {alpha, eps}, s0 .. s4 = init_particles, cumulative_gradients C, scale L (created at eps), subgradients G, reward R
+ *                    (cocob.py:52-86): L = max(L, |fg|); G += |fg|; R = max(R - fg (x - x0), 0); C -= fg;
+ *                    x += -x + (x0 + C / (L max(G + L, alpha L)) (L + R)).
+ *   sgd / adagrad / adam restate optax's published formulas; their parity with optax itself is not pinned by a test.
+ * mfm_svgd_step: n_iter whole iterations on the context's target at temperature beta, on the n_chain_valid particles of d_x
+ *   [n_chain_local][dim] (padding rows are never read into a sum nor written): target gradient (the launch of mfm_mala_init), sqdist
+ *   (kept from the previous iteration's last step: same bits), gradient, apply with count + iteration, then sqdist of the new
+ *   particles and, unless update_median == 0, median into d_length_scale[0] (in: the scale of the first iteration).  d_ls_used (may
+ *   be NULL): float64 [n_iter], the scale each iteration used.  n_chain_total != n_chain_local: MFM_EUNSUPPORTED.  The bits of n_iter
+ *   calls with n_iter = 1. */
+enum { MFM_SVGD_SGD = 0, MFM_SVGD_ADAGRAD = 1, MFM_SVGD_ADAM = 2, MFM_SVGD_COCOB = 3 };
+int mfm_svgd_sqdist(mfm_ctx* ctx, const float* d_x, int32_t n, int32_t d, float* d_D);
+int mfm_svgd_median(mfm_ctx* ctx, const float* d_D, int32_t n, double* d_length_scale);
+int mfm_svgd_gradient(mfm_ctx* ctx, const float* d_x, const float* d_g, const float* d_D, const double* d_length_scale, int32_t n, int32_t d,
+                      int32_t i0, int32_t n_rows, float* d_fg);
+int mfm_svgd_apply(mfm_ctx* ctx, int kind, const double* h_hyper, int64_t count, int32_t n, int32_t d, float* d_x, const float* d_fg,
+                   float* d_s0, float* d_s1, float* d_s2, float* d_s3, float* d_s4);
+int mfm_svgd_step(mfm_ctx* ctx, double beta, int kind, const double* h_hyper, int64_t count, int32_t n_iter, int update_median, float* d_x,
+                  float* d_s0, float* d_s1, float* d_s2, float* d_s3, float* d_s4, double* d_length_scale, double* d_ls_used);
+
 /* ---- algorithmic counters (the figures roofline numbers are computed from) ----------------------
  * h_out[0] MALA chain-steps, [1] flow-matching training samples, [2] flow-matching evaluation samples (mfm_fm_loss),
  * [3] Dopri5 solves (a flow step is two per chain), [4] attempted Dopri5 steps over all solves (summed on the device),

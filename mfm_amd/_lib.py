@@ -42,6 +42,8 @@ class Config(C.Structure):
 MAX_DEPTH = 3          # include/mfm.h: MFM_MAX_DEPTH
 AUTOCORR_LAG_BLOCK, AUTOCORR_TIME_BLOCK = 32, 256      # include/mfm.h: MFM_AUTOCORR_LAG_BLOCK / _TIME_BLOCK (lags per pass, float32 time block)
 ODE_METHODS = {"dopri5": 0, "rk4": 1, "euler": 2}      # include/mfm.h: MFM_ODE_*
+SVGD_OPTIMIZERS = {"sgd": 0, "adagrad": 1, "adam": 2, "cocob": 3}      # include/mfm.h: MFM_SVGD_*
+SVGD_N_STATE = {"sgd": 0, "adagrad": 1, "adam": 2, "cocob": 5}         # state arrays [n, d] of each kind
 
 
 _P = C.c_void_p
@@ -109,6 +111,11 @@ _SIGS = {
     "mfm_autocorr": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_chain_sums": (C.c_int, [_P, _P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "mfm_chain_diag": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P]),
+    "mfm_svgd_sqdist": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P]),
+    "mfm_svgd_median": (C.c_int, [_P, _P, C.c_int32, _P]),
+    "mfm_svgd_gradient": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "mfm_svgd_apply": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_svgd_step": (C.c_int, [_P, C.c_double, C.c_int, C.POINTER(C.c_double), C.c_int64, C.c_int32, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_noise_prefetch": (C.c_int, [_P, C.c_int, C.POINTER(_U32), C.POINTER(_U32)]),
     "mfm_noise_drop": (C.c_int, [_P]),
     "mfm_get_counters": (C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -738,6 +745,43 @@ class Context:
                 raise MfmError(f"chain_diag: {name} must have shape {want}, got {tuple(t_.shape)}")
         _chk(self.lib.mfm_chain_diag(self.h, _ptr(sums, F64), int(n_sub), int(n_subchains), dim, n_lags, _ptr(rhat, F32), _ptr(ess, F32),
                                      _ptr(tau, F32), _ptr(rho, F32)))
+
+    # ---- Stein variational gradient descent (include/mfm.h: mfm_svgd_*) -------------------------------------------------------------
+    def svgd_sqdist(self, x, D):
+        """``D [n, n]`` float32 = squared distances of the float32 CUDA particles ``x [n, d]`` (any n >= 2, d >= 1)."""
+        _chk(self.lib.mfm_svgd_sqdist(self.h, _ptr(x, F32), int(x.shape[0]), int(x.shape[1]), _ptr(D, F32)))
+
+    def svgd_median(self, D, length_scale):
+        """``length_scale`` (float64 CUDA tensor of one element) = median heuristic of the strict lower triangle of ``D [n, n]``."""
+        _chk(self.lib.mfm_svgd_median(self.h, _ptr(D, F32), int(D.shape[0]), _ptr(length_scale, F64)))
+
+    def svgd_gradient(self, x, g, D, length_scale, fg, i0=0, n_rows=None):
+        """``fg [n_rows, d]`` = rows ``[i0, i0 + n_rows)`` (default: all) of the functional gradient of ``x, g [n, d]`` under ``D`` and the
+        device scalar ``length_scale``."""
+        n = int(x.shape[0])
+        _chk(self.lib.mfm_svgd_gradient(self.h, _ptr(x, F32), _ptr(g, F32), _ptr(D, F32), _ptr(length_scale, F64), n, int(x.shape[1]),
+                                        int(i0), int(n - int(i0) if n_rows is None else n_rows), _ptr(fg, F32)))
+
+    @staticmethod
+    def _svgd_opt(kind, hyper, state):
+        if kind not in SVGD_OPTIMIZERS:
+            raise MfmError(f"svgd: unknown optimizer kind {kind!r} (one of {', '.join(SVGD_OPTIMIZERS)})")
+        hp = (C.c_double * 4)(*([float(v) for v in hyper] + [0.0] * 4)[:4])
+        st = [_ptr(t, F32) for t in state] + [None] * 5
+        return SVGD_OPTIMIZERS[kind], hp, st[:5]
+
+    def svgd_apply(self, kind, hyper, count, x, fg, state=()):
+        """One optimizer update of ``x [n, d]`` in place from ``fg``; ``state``: the kind's float32 arrays ``[n, d]``, updated in place;
+        ``count``: updates already applied."""
+        k, hp, st = self._svgd_opt(kind, hyper, state)
+        _chk(self.lib.mfm_svgd_apply(self.h, k, hp, int(count), int(x.shape[0]), int(x.shape[1]), _ptr(x, F32), _ptr(fg, F32), *st))
+
+    def svgd_step(self, beta, kind, hyper, count, n_iter, x, state, length_scale, update_median=True, ls_used=None):
+        """``n_iter`` SVGD iterations in place on the ``n_chain_valid`` particles of ``x [n_chain_local, dim]``; ``length_scale``: float64
+        CUDA tensor of one element (in / out); ``ls_used``: optional float64 ``[n_iter]``, the scale every iteration used."""
+        k, hp, st = self._svgd_opt(kind, hyper, state)
+        _chk(self.lib.mfm_svgd_step(self.h, float(beta), k, hp, int(count), int(n_iter), int(bool(update_median)), _ptr(x, F32), *st,
+                                    _ptr(length_scale, F64), _ptr(ls_used, F64)))
 
     def beta_update(self, prev_beta, logliks, alpha):
         out = C.c_double()

@@ -1,2 +1,3 @@
-"""Kernel API of the reference's vendored ``bblackjax`` for the MFM hot path (MALA only)."""
+"""Kernel API of the reference's vendored ``bblackjax`` on MI355X: ``mcmc`` (MALA -- the MFM hot path, SURVEY.md section 8a M1-M4 -- and
+the build-side HMC / NUTS), ``adaptation``, ``smc``, and ``vi`` / ``optimizers`` (Stein variational gradient descent and its optimizers)."""
 from .mcmc.mala import mala  # noqa: F401

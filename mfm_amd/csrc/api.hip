@@ -30,6 +30,7 @@
 #include "cis.hip"
 #include "wide.hip"
 #include "smc.hip"
+#include "svgd.hip"
 
 static thread_local char g_err[512] = "";
 static int fail(int code, const char* fmt, ...) {
@@ -108,6 +109,8 @@ struct mfm_ctx {
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* cs_ws = nullptr; size_t cs_ws_cap = 0;     // mfm_chain_sums: mean and A_0 of every sub-chain, then the slabs [n_slices][n_lags + 2][dim] of float64 partial sums
   void* run_ws = nullptr; size_t run_ws_cap = 0;  // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
+  void* svgd_ws = nullptr; size_t svgd_ws_cap = 0;        // mfm_svgd_*: column means, centred coordinates, row norms, selection state (svgd.hip: Scratch)
+  void* svgd_step_ws = nullptr; size_t svgd_step_ws_cap = 0;   // mfm_svgd_step: D [n][n], the functional gradient, the target's log-density and gradient
   mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
   // mfm_hmc_set_inverse_mass: the diagonal of the HMC kernels' inverse mass matrix.  d_inv_mass [dim] holds the installed vector, or
   // ones when none is set (mfm_hmc_warmup_window runs the mass instances either way); h_inv_mass is the host copy, empty when none is set
@@ -398,7 +401,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -1731,6 +1734,129 @@ extern "C" int mfm_chain_diag(mfm_ctx* x, const double* d_sums, int64_t n_sub, i
   if (!d_rhat && !d_ess && !d_tau && !d_rho) return fail(MFM_EINVAL, "every output (d_rhat, d_ess, d_tau, d_rho) is null");
   launch_chain_diag(d_sums, n_sub, n_subchains, dim, n_lags, d_rhat, d_ess, d_tau, d_rho, x->stream);
   LAUNCHCHK();
+  return MFM_OK;
+}
+
+// ---- Stein variational gradient descent (svgd.hip; bblackjax/vi/svgd.py, optimizers/cocob.py) -----------------------------------------
+#define MFM_SVGD_MAX_N 16384      /* D [n][n] float32 passes 1 GiB beyond */
+static int svgd_grow(mfm_ctx* x, void*& p, size_t& cap, size_t need) {
+  if (cap >= need) return MFM_OK;
+  if (p) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(p); p = nullptr; cap = 0; }
+  HIPCHK(hipMalloc(&p, need));
+  cap = need;
+  return MFM_OK;
+}
+static int svgd_check_shape(int32_t n, int32_t d) {
+  if (n > MFM_SVGD_MAX_N) return fail(MFM_ETOOLARGE, "n = %d particles exceed %d (the distance matrix would pass 1 GiB)", n, MFM_SVGD_MAX_N);
+  if (n < 2) return fail(MFM_EINVAL, "n must be at least 2 (got %d)", n);
+  if (d < 1) return fail(MFM_EINVAL, "d must be at least 1 (got %d)", d);
+  return MFM_OK;
+}
+static int svgd_scratch(mfm_ctx* x, int32_t n, int32_t d, svgd::Scratch* s) {
+  CHECKED(svgd_grow(x, x->svgd_ws, x->svgd_ws_cap, svgd::scratch_bytes(n, d)));
+  *s = svgd::carve(x->svgd_ws, n, d);
+  return MFM_OK;
+}
+
+extern "C" int mfm_svgd_sqdist(mfm_ctx* x, const float* d_x, int32_t n, int32_t d, float* d_D) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (!d_D) return fail(MFM_EINVAL, "d_D is null");
+  CHECKED(svgd_check_shape(n, d));
+  svgd::Scratch s; CHECKED(svgd_scratch(x, n, d, &s));
+  svgd::launch_sqdist(s, d_x, n, d, d_D, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+extern "C" int mfm_svgd_median(mfm_ctx* x, const float* d_D, int32_t n, double* d_length_scale) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_D) return fail(MFM_EINVAL, "d_D is null");
+  if (!d_length_scale) return fail(MFM_EINVAL, "d_length_scale is null");
+  CHECKED(svgd_check_shape(n, 1));
+  svgd::Scratch s; CHECKED(svgd_scratch(x, n, 1, &s));
+  svgd::launch_median(s, d_D, n, d_length_scale, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+extern "C" int mfm_svgd_gradient(mfm_ctx* x, const float* d_x, const float* d_g, const float* d_D, const double* d_length_scale, int32_t n, int32_t d,
+                                 int32_t i0, int32_t n_rows, float* d_fg) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (!d_g) return fail(MFM_EINVAL, "d_g is null");
+  if (!d_D) return fail(MFM_EINVAL, "d_D is null");
+  if (!d_length_scale) return fail(MFM_EINVAL, "d_length_scale is null");
+  if (!d_fg) return fail(MFM_EINVAL, "d_fg is null");
+  CHECKED(svgd_check_shape(n, d));
+  if (i0 < 0 || n_rows < 1 || (int64_t)i0 + n_rows > n) return fail(MFM_EINVAL, "row range [i0 = %d, i0 + n_rows = %lld) must lie in [0, n = %d) and hold a row", i0, (long long)i0 + n_rows, n);
+  svgd::Scratch s; CHECKED(svgd_scratch(x, n, d, &s));
+  svgd::launch_gradient(s, d_x, d_g, d_D, d_length_scale, n, d, i0, n_rows, d_fg, false, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+static int svgd_check_opt(int kind, const double* h_hyper, int64_t count, float* const* st) {
+  if (kind < MFM_SVGD_SGD || kind > MFM_SVGD_COCOB) return fail(MFM_EINVAL, "unknown optimizer kind %d (0 sgd, 1 adagrad, 2 adam, 3 cocob)", kind);
+  if (!h_hyper) return fail(MFM_EINVAL, "h_hyper is null");
+  if (count < 0) return fail(MFM_EINVAL, "count must not be negative (got %lld)", (long long)count);
+  const int n_state = kind == MFM_SVGD_SGD ? 0 : kind == MFM_SVGD_ADAGRAD ? 1 : kind == MFM_SVGD_ADAM ? 2 : 5;
+  for (int i = 0; i < n_state; ++i) if (!st[i]) return fail(MFM_EINVAL, "d_s%d is null (optimizer kind %d has %d state arrays)", i, kind, n_state);
+  return MFM_OK;
+}
+static svgd::ApplyArgs svgd_apply_args(int kind, const double* h_hyper, int64_t count, int32_t n, int32_t d, float* d_x, const float* d_fg, float* const* st) {
+  svgd::ApplyArgs a; a.kind = kind; a.count = count; a.total = (size_t)n * d; a.x = d_x; a.fg = d_fg;
+  for (int i = 0; i < 4; ++i) a.hp[i] = h_hyper[i];
+  for (int i = 0; i < 5; ++i) a.s[i] = st[i];
+  return a;
+}
+
+extern "C" int mfm_svgd_apply(mfm_ctx* x, int kind, const double* h_hyper, int64_t count, int32_t n, int32_t d, float* d_x, const float* d_fg,
+                              float* d_s0, float* d_s1, float* d_s2, float* d_s3, float* d_s4) { use_ctx(x);
+  if (!x) return fail(MFM_EINVAL, "null ctx");
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (!d_fg) return fail(MFM_EINVAL, "d_fg is null");
+  float* st[5] = {d_s0, d_s1, d_s2, d_s3, d_s4};
+  CHECKED(svgd_check_opt(kind, h_hyper, count, st));
+  if (n < 1 || d < 1) return fail(MFM_EINVAL, "n and d must be at least 1 (got %d, %d)", n, d);
+  svgd::launch_apply(svgd_apply_args(kind, h_hyper, count, n, d, d_x, d_fg, st), x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+extern "C" int mfm_svgd_step(mfm_ctx* x, double beta, int kind, const double* h_hyper, int64_t count, int32_t n_iter, int update_median, float* d_x,
+                             float* d_s0, float* d_s1, float* d_s2, float* d_s3, float* d_s4, double* d_length_scale, double* d_ls_used) { use_ctx(x);
+  NEED_TARGET();
+  if (x->cfg.n_chain_total != x->cfg.n_chain_local)
+    return fail(MFM_EUNSUPPORTED, "n_chain_total = %d differs from n_chain_local = %d: SVGD over more than one rank is not built", x->cfg.n_chain_total, x->cfg.n_chain_local);
+  const int32_t B = x->cfg.n_chain_local, d = x->cfg.dim;
+  const int32_t n = x->cfg.n_chain_valid > 0 ? x->cfg.n_chain_valid : B;
+  CHECKED(svgd_check_shape(n, d));
+  if (n_iter < 1) return fail(MFM_EINVAL, "n_iter must be at least 1 (got %d)", n_iter);
+  float* st[5] = {d_s0, d_s1, d_s2, d_s3, d_s4};
+  CHECKED(svgd_check_opt(kind, h_hyper, count, st));
+  if (!d_x) return fail(MFM_EINVAL, "d_x is null");
+  if (!d_length_scale) return fail(MFM_EINVAL, "d_length_scale is null");
+  svgd::Scratch s; CHECKED(svgd_scratch(x, n, d, &s));
+  const size_t nD = ((size_t)n * n * 4 + 255) & ~(size_t)255, nG = ((size_t)B * d * 4 + 255) & ~(size_t)255, nF = ((size_t)n * d * 4 + 255) & ~(size_t)255;
+  CHECKED(svgd_grow(x, x->svgd_step_ws, x->svgd_step_ws_cap, nD + nG + nF + (size_t)B * 8));
+  char* base = (char*)x->svgd_step_ws;
+  float* D = (float*)base; float* g = (float*)(base + nD); float* fg = (float*)(base + nD + nG); double* logp = (double*)(base + nD + nG + nF);
+  bool have_D = false;           // D and the scratch's centred coordinates belong to the particles as they stand
+  for (int32_t it = 0; it < n_iter; ++it) {
+    CHECKED(mfm_mala_init(x, d_x, beta, logp, g));                 // the target's gradient at every row (the padding rows' is not read)
+    if (d_ls_used) HIPCHK(hipMemcpyAsync(d_ls_used + it, d_length_scale, sizeof(double), hipMemcpyDeviceToDevice, x->stream));
+    if (!have_D) svgd::launch_sqdist(s, d_x, n, d, D, x->stream);
+    svgd::launch_gradient(s, d_x, g, D, d_length_scale, n, d, 0, n, fg, true, x->stream);
+    svgd::launch_apply(svgd_apply_args(kind, h_hyper, count + it, n, d, d_x, fg, st), x->stream);
+    have_D = false;
+    if (update_median || it + 1 < n_iter) {                        // sqdist is a pure function of the particles: kept for the next iteration, same bits
+      svgd::launch_sqdist(s, d_x, n, d, D, x->stream);
+      have_D = true;
+      if (update_median) svgd::launch_median(s, D, n, d_length_scale, x->stream);
+    }
+    LAUNCHCHK();
+  }
   return MFM_OK;
 }
 

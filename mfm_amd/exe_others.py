@@ -1,6 +1,8 @@
-"""Baseline runners -- drop-in for the reference's ``exe_others.py``, for the ONE baseline that shares the MFM hot path:
-adaptive tempered SMC on the MALA kernel (``exe_others.py:79-111``).  The other baselines
-(flowMC, pocoMC, DDS, FAB: ``:44-76,114-296``) wrap third-party samplers outside the scope and raise.
+"""Baseline runners -- drop-in for the reference's ``exe_others.py``, for the baselines that share the MFM hot path:
+adaptive tempered SMC on the MALA kernel (``exe_others.py:79-111``) and -- ``--do_svgd``, a build-side
+baseline the reference's script does not run -- Stein variational gradient descent on the same particles and target gradients
+(``bblackjax/vi/svgd.py``; ``mfm_svgd_step``).  The other baselines (flowMC, pocoMC, DDS, FAB: ``:44-76,114-296``) wrap third-party
+samplers outside the scope and raise.
 
 ``run(dist, args, target_gn=None) -> (res[5], res_[5])`` as ``exe_others.py:22,376``: logpdf, Stein U / V, MMD, train time
 for the collected particles (the reference reports the same MCMC particles as "flow" and "exact" samples, ``:108-109``).
@@ -14,6 +16,8 @@ from . import random as jr
 from . import wandb_shim as wandb
 from .bblackjax.mcmc import mala
 from .bblackjax.smc import adaptive_tempered, base as smc_base, resampling
+from .bblackjax import optimizers
+from .bblackjax.vi import svgd as svgd_module
 from .engine import Engine, allgather_cat
 from .exe_flow_matching import _logprob_any, stein_disc
 
@@ -23,6 +27,8 @@ logger = logging.getLogger(__name__)
 def run(dist, args, target_gn=None, return_extras=False):
     import torch
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO)
+    if getattr(args, "do_svgd", False) and not getattr(args, "do_smc", False):
+        return run_svgd(dist, args, target_gn, return_extras)
     if not getattr(args, "do_smc", False):
         raise NotImplementedError("only --do_smc (adaptive tempered SMC on the MALA kernel) is built; flowMC / pocoMC / DDS / FAB "
                                   "wrap third-party samplers outside the hot-path scope (SURVEY.md section 2)")
@@ -73,5 +79,55 @@ def run(dist, args, target_gn=None, return_extras=False):
     wandb.finish()
     if return_extras:
         return res, res_, dict(lmbdas=np.array(lmbdas), state=state, engine=eng, samples=flow_samples)
+    eng.close()
+    return res, res_
+
+
+def svgd_optimizer(args):
+    """The descriptor ``--svgd_optimizer`` / ``--svgd_step_size`` name (cocob is parameter-free: the step size plays no part)."""
+    kind, lr = getattr(args, "svgd_optimizer", "adagrad"), float(getattr(args, "svgd_step_size", 0.1))
+    if kind not in ("sgd", "adagrad", "adam", "cocob"):
+        raise ValueError(f"--svgd_optimizer must be one of sgd, adagrad, adam, cocob (got {kind!r})")
+    return optimizers.cocob.cocob() if kind == "cocob" else getattr(optimizers, kind)(lr)
+
+
+def run_svgd(dist, args, target_gn=None, return_extras=False):
+    """``--do_svgd``: ``learning_iter`` SVGD iterations on the initial particles at beta = 1, in ONE library call (the length scale of
+    every iteration comes back with it and is logged every ``--log_every``-th); ``res[5]`` in ``--do_smc``'s shape for the final particles."""
+    import torch
+    learning_iter, n_chain = int(args.learning_iter), int(args.num_chain)
+    key_target, key_sample, key_init, key_dist, key_fourier, key_gen = jr.split(jr.PRNGKey(args.seed), 6)     # :33
+    dist.initialize_model(key_dist, n_chain)                                                # :34
+    eng = Engine(dist, args, None, max_eval_samples=n_chain)
+    if eng.world > 1:
+        eng.close()
+        raise NotImplementedError("the SVGD baseline runs on one rank (every particle interacts with every other; mfm_svgd_step refuses a sharded context)")
+    real_samples = None
+    if target_gn is not None:                                                               # :36-39
+        key_gen, key_loss = jr.split(key_target)
+        real_samples = torch.as_tensor(np.ascontiguousarray(dist.sample_rows(jr.split(key_gen, n_chain)), dtype=np.float32), device=eng.dev)
+    logger.info(f"===== Starting training seed {args.seed} w/ {learning_iter} iterations =====")
+    logger.info(f"Stein variational gradient descent, optimizer {getattr(args, 'svgd_optimizer', 'adagrad')}")
+    algo = svgd_module.svgd(dist.grad_logprob, svgd_optimizer(args))
+    state = algo.init(eng.local(dist.init_params))
+    train_start = time.time()
+    state, length_scales = algo.step.run(state, learning_iter, keep_length_scales=True)
+    eng.ctx.sync()
+    train_time = time.time() - train_start
+    length_scales = length_scales.cpu().numpy()
+    log_every = max(1, int(getattr(args, "log_every", 1) or 1))
+    for it in range(0, learning_iter, log_every):
+        wandb.log({"iteration": it, "length_scale": float(length_scales[it])})
+    particles = state.particles[:eng.n_valid].contiguous()
+    logpdf = _logprob_any(eng, particles).mean().item()
+    stein = stein_disc(eng, particles)
+    mmd = eng.ctx.max_mean_disc(real_samples, particles) if real_samples is not None else 0.0
+    wandb.log({"train_time": train_time, "logpdf": logpdf, "KSD U-stat": stein[0], "KSD V-stat": stein[1],
+               "length_scale": float(state.kernel_parameters["length_scale"].item())})
+    res = np.array([logpdf, stein[0], stein[1], mmd, train_time])
+    res_ = res.copy()                                                                       # same particles, as the SMC baseline (:108-109)
+    wandb.finish()
+    if return_extras:
+        return res, res_, dict(length_scales=length_scales, state=state, engine=eng, samples=particles)
     eng.close()
     return res, res_

@@ -6,7 +6,7 @@ values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=25
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
 ``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic),
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
-``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); the other baselines
+``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
 
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N -m mfm_amd.multi_modal ...``; chains are
@@ -78,12 +78,14 @@ def main(args):
     job_type = "mcmc_per_flow_steps=" + str(args.mcmc_per_flow_steps) + ",learning_iter=" + str(args.learning_iter) + (",hutchs" if args.hutchs else "")
     if args.do_smc:
         job_type = "Adaptive tempered SMC"                                              # :110-111
+    elif args.do_svgd:
+        job_type = "SVGD"
     seeds = [args.seed] if args.seed else [i ** 10 for i in range(10)]                  # :118
     res, res_ = [], []
     for seed in seeds:
         args.seed = seed
         wandb.init(project=args.example, config=args, group="dim=" + str(N_PARAM), job_type=job_type)
-        if args.do_smc:
+        if args.do_smc or args.do_svgd:
             _res, _res_ = run_others(dist, args, dist.sample_model)                     # :126-127
         else:
             _res, _res_ = run(dist, args, dist.sample_model, log_every=args.log_every)  # :129
@@ -180,6 +182,12 @@ def build_parser():
     # with --mcmc_kernel nuts --adapt_steps N: 'hmc' runs the HMC warmup with --hmc_steps leapfrog steps and hands its step size (and mass) to
     # NUTS; 'tree' runs NUTS's own warmup under --max_tree_depth, adapting on the trees' acceptance statistic (--hmc_steps plays no part)
     parser.add_argument('--nuts_adapt', type=str, default='hmc', choices=['hmc', 'tree'])
+    # the SVGD baseline (exe_others.run_svgd): --learning_iter iterations of Stein variational gradient descent on the initial particles at
+    # beta = 1 under the named optimizer (bblackjax/optimizers); cocob is parameter-free and ignores --svgd_step_size
+    parser.add_argument('--do_svgd', dest='do_svgd', action='store_true')
+    parser.set_defaults(do_svgd=False)
+    parser.add_argument('--svgd_optimizer', type=str, default='adagrad', choices=['sgd', 'adagrad', 'adam', 'cocob'])
+    parser.add_argument('--svgd_step_size', type=float, default=0.1)
     return parser
 
 
