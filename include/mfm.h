@@ -276,6 +276,50 @@ int mfm_hmc_warmup_window(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t ke
                           int32_t* d_n_accepted, double* d_acc_sum,
                           double* d_step_traj,
                           double* d_pos_sum, double* d_pos_sumsq);
+/* mfm_hmc_run with ONE LEAPFROG COUNT PER STEP: d_num_steps is int32[n_steps] in device memory, every entry in [1, 100000] (the host
+ * cannot see the array: the kernel clamps an entry into that range), and step j has the bits of mfm_hmc_step / mfm_hmc_step_keys with
+ * num_steps = d_num_steps[j] on mfm_hmc_run's step key.  The count is the same for every chain of a step, so the chains stay in lock
+ * step: this is the sampler mfm_chees_warmup adapts, the host filling the array from the jitter sequence.  Everything else -- key_mode,
+ * keys, tallies, thin and the trajectory, the checks and their order, with d_num_steps (non-null) in num_steps' place -- is
+ * mfm_hmc_run's.  d_total_leapfrog (or NULL): int64 scalar, the leapfrog steps of one chain over the run, the sum of the entries. */
+int mfm_hmc_run_lengths(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                        double beta, double step_size, const int32_t* d_num_steps /* [n_steps] leapfrog steps of each HMC step */,
+                        int32_t n_steps, int32_t thin,
+                        float* d_pos, double* d_logp, float* d_grad,
+                        int32_t* d_n_accepted, double* d_acc_sum,
+                        float* d_acceptance_rate, uint8_t* d_is_accepted,
+                        float* d_traj_pos, double* d_traj_logp,
+                        int64_t* d_total_leapfrog);
+/* ChEES-HMC WARMUP (Hoffman, Radul & Sountsov 2021; blackjax's chees_adaptation): n_iter HMC steps of ALL chains in which the step size
+ * and the trajectory length are adapted ACROSS the chains; tests/chees_ref.py restates it in float64 and is the definition.  The call
+ * only enqueues (four launches per iteration, chees.hip); eps_t, T_t, L_t and the optimizer's state live in device memory.
+ * Iteration t = 1 .. n_iter, with eps_1 = step0 and T_1 = traj0:
+ *   1. h_t = the base-2 radical inverse of t (1/2, 1/4, 3/4, 1/8, ...), tau_t = h_t T_t, L_t = min(max_leapfrog, max(1, ceil(tau_t / eps_t)));
+ *   2. one HMC step of every chain with (eps_t, L_t) on the key mfm_hmc_run (n_steps = n_iter, same key_mode) uses for step t - 1: the
+ *      bits of mfm_hmc_step_keys.  Kept per chain: the state before the step x, the end point x' (float32, accepted or not), the end
+ *      velocity v' = minv p', alpha = min(1, exp(H_0 - H_end)), and div = !(H_end - H_0 < divergence_threshold) (NaN: divergent);
+ *   3. over the first n_valid chains (rows from n_valid on are stepped but not read), in float64: the column means xbar, xbar' over
+ *      all of them; over the non-divergent ones, g_k = tau_t (|x'_k - xbar'|^2 - |x_k - xbar|^2) <x'_k - xbar', v'_k>,
+ *      ghat_t = sum alpha_k g_k / sum (alpha_k + 1e-20), hm_t = n / sum (1 / alpha_k) (IEEE: an alpha of 0 gives 0); all divergent: both 0;
+ *   4. the step size by mfm_hmc_warmup's dual averaging, steps 2. - 5. above with p_m := hm_t, giving eps_{t+1} = exp(x_t);
+ *   5. one Adam step (b1 0.9, b2 0.999, epsilon 1e-8, bias-corrected) ASCENDING log T along ghat_t; a non-finite ghat_t leaves log T and
+ *      the moments as they were; then log T is clamped to [x_t, x_t + log(max_leapfrog)], T_{t+1} = exp(log T), and
+ *      ma_t = decay ma_{t-1} + (1 - decay) log T_{t+1} with ma_0 = log(traj0).
+ * h_result (host, or NULL) takes {exp(xbar_n), exp(ma_n), eps_{n+1}, T_{n+1}}: the step size and the trajectory length to sample with,
+ * and the last iterates.  With it the call ends by waiting for the stream; with NULL it returns without any host synchronisation.
+ * d_trace (or NULL): double[n_iter][7] = eps_t, T_t, L_t, hm_t, ghat_t, the number of divergent chains, the mean alpha over the valid
+ * chains.  d_prop float[B][dim], d_vel double[B][dim], d_alpha double[B] (each or NULL: context scratch) are left holding the LAST
+ * iteration's x', v', alpha.  State is updated in place; the context's inverse mass (mfm_hmc_set_inverse_mass) is used as given.
+ * Checks: mfm_hmc_run's shared ones in its order (state and step0, key_mode / d_keys / n_iter, the Cox process: MFM_EUNSUPPORTED with
+ * mfm_hmc_step's message), then n_chain_total != n_chain_local: MFM_EUNSUPPORTED (the means would need an all-reduce); n_valid outside
+ * [2, n_chain_local], traj0 or learning_rate not positive, decay outside [0, 1), max_leapfrog outside [1, 100000], target_accept
+ * outside (0, 1), divergence_threshold not positive: MFM_EINVAL.  A rejected call touches nothing. */
+int mfm_chees_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                     double beta, double step0, double traj0,
+                     int32_t n_iter, int32_t n_valid, double target_accept, double learning_rate,
+                     int32_t max_leapfrog, double decay, double divergence_threshold,
+                     float* d_pos, double* d_logp, float* d_grad,
+                     double* h_result /* [4] */, double* d_trace, float* d_prop, double* d_vel, double* d_alpha);
 /* STEP-SIZE WARMUP OF THE NO-U-TURN SAMPLER: n_steps NUTS transitions in ONE launch, as mfm_nuts_run (chain resident in registers,
  * key_mode 0 / 1 and their key schedules, max_tree_depth / divergence_threshold and the installed inverse mass as there), in which every
  * chain adapts its OWN step size by the dual averaging of mfm_hmc_warmup -- the same recursion, constants and clamp, eps_1 = step0

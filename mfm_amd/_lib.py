@@ -68,6 +68,9 @@ _SIGS = {
     "mfm_hmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
     "mfm_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_hmc_run_lengths": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_chees_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
+                                   C.c_int32, C.c_double, C.c_double, _P, _P, _P, C.POINTER(C.c_double), _P, _P, _P, _P]),
     "mfm_nuts_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, _P, _P, _P,
@@ -351,6 +354,43 @@ class Context:
                                   int(num_steps), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                   _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
                                   _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    def hmc_run_lengths(self, key, beta, step_size, num_steps, pos, logp, grad, thin=0, n_acc=None, acc_sum=None, acc=None, is_acc=None,
+                        traj_pos=None, traj_logp=None, total_leapfrog=None, key_mode=None):
+        """``mfm_hmc_run_lengths``: ``hmc_run`` with ``num_steps`` an int32 device tensor ``[n_steps]``, the leapfrog steps of each HMC
+        step (every entry in [1, 100000]); ``total_leapfrog`` (int64 device tensor of one element, optional) takes their sum."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        n_steps = 0 if num_steps is None else int(num_steps.numel())
+        _chk(self.lib.mfm_hmc_run_lengths(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size),
+                                          _ptr(num_steps, I32), n_steps, int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                          _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
+                                          _ptr(traj_pos, F32), _ptr(traj_logp, F64), _ptr(total_leapfrog, I64)))
+
+    def chees_warmup(self, key, beta, step0, n_iter, pos, logp, grad, traj0=None, n_valid=None, target_accept=0.651, learning_rate=0.025,
+                     max_leapfrog=1000, decay=0.5, divergence_threshold=1000.0, trace=None, prop=None, vel=None, alpha=None, key_mode=None,
+                     read_result=True):
+        """``mfm_chees_warmup``: ``n_iter`` ChEES-HMC iterations, the step size and the trajectory length adapted across the chains
+        (the algorithm: ``include/mfm.h``, ``tests/chees_ref.py``); state updated in place.  ``key`` / ``key_mode`` as ``hmc_run``'s.
+        ``traj0`` defaults to ``step0`` (one leapfrog step), ``n_valid`` to every chain.  Optional device tensors: ``trace`` float64
+        ``[n_iter, 7]``; ``prop`` float32 ``[n, dim]``, ``vel`` float64 ``[n, dim]``, ``alpha`` float64 ``[n]``, the last iteration's
+        records.  Returns ``(step_size, trajectory_length, last_step_size, last_trajectory_length)``, which waits for the stream, or
+        ``None`` with ``read_result=False`` (no host synchronisation at all)."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        n = self.n_local
+        for name, t_, need in (("trace", trace, max(int(n_iter), 0) * 7), ("prop", prop, n * self.dim), ("vel", vel, n * self.dim), ("alpha", alpha, n)):
+            if t_ is not None and t_.numel() < need:
+                raise MfmError(f"{name} must hold {need} elements (got {t_.numel()})")
+        res = (C.c_double * 4)() if read_result else None
+        _chk(self.lib.mfm_chees_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
+                                       float(step0 if traj0 is None else traj0), int(n_iter), int(n if n_valid is None else n_valid),
+                                       float(target_accept), float(learning_rate), int(max_leapfrog), float(decay), float(divergence_threshold),
+                                       _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), res, _ptr(trace, F64), _ptr(prop, F32),
+                                       _ptr(vel, F64), _ptr(alpha, F64)))
+        return tuple(res) if read_result else None
 
     def _nuts_info(self, depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy):
         return (_ptr(depth, I32), _ptr(num_leapfrog, I32), _ptr(is_turning, U8), _ptr(is_divergent, U8), _ptr(acceptance_rate, F64), _ptr(energy, F64))

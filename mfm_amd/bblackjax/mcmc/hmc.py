@@ -23,7 +23,7 @@ from ...distributions import resolve_logdensity
 from ..base import SamplingAlgorithm
 from .mala import MALAState as HMCState, _engine, init
 
-__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "HMCWarmupInfo", "init", "build_kernel", "hmc", "check_inverse_mass"]
+__all__ = ["HMCState", "HMCInfo", "HMCRunInfo", "HMCRunLengthsInfo", "HMCWarmupInfo", "init", "build_kernel", "hmc", "check_inverse_mass", "integration_step_counts"]
 
 
 def check_inverse_mass(inverse_mass_matrix, dim=None):
@@ -51,12 +51,24 @@ class HMCInfo(NamedTuple):
 class HMCRunInfo(NamedTuple):
     """What ``kernel.run`` reports, field for field ``MALARunInfo``: per chain the mean acceptance probability and the number of
     accepted steps, the LAST step's ``HMCInfo``, and (with ``thin``) the kept states ``positions [num_steps / thin, n_chain, dim]`` /
-    ``logdensities [num_steps / thin, n_chain]`` (``None`` without)."""
+    ``logdensities [num_steps / thin, n_chain]`` (``None`` without).  ``num_leapfrog`` is an attribute beside the five tuple fields
+    (which stay ``MALARunInfo``'s): ``None``, or for a run with ``num_integration_steps_per_step`` (an ``HMCRunLengthsInfo``) the leapfrog
+    steps of one chain over the run."""
     acceptance_rate: object
     num_accepted: object
     last: HMCInfo
     positions: object
     logdensities: object
+    num_leapfrog = None
+
+
+class HMCRunLengthsInfo(HMCRunInfo):
+    """``HMCRunInfo`` of a run with one leapfrog count per step: the same tuple, and ``num_leapfrog`` (int), their sum."""
+
+    def __new__(cls, acceptance_rate, num_accepted, last, positions, logdensities, num_leapfrog):
+        self = super().__new__(cls, acceptance_rate, num_accepted, last, positions, logdensities)
+        self.num_leapfrog = num_leapfrog
+        return self
 
 
 class HMCWarmupInfo(NamedTuple):
@@ -96,6 +108,19 @@ def _device_keys(t, rng_key, dev):
     return rng_key if t.is_tensor(rng_key) else t.as_tensor(np.ascontiguousarray(rng_key, dtype=np.uint32).view(np.int32), device=dev)
 
 
+def integration_step_counts(per_step, num_steps):
+    """``num_integration_steps_per_step`` as an int32 array ``[num_steps]``: an array-like of that length, or a callable ``i -> int``;
+    ``ValueError`` for a wrong length or an entry outside [1, 100000] (before any device work)."""
+    num_steps = int(num_steps)
+    v = [per_step(i) for i in range(num_steps)] if callable(per_step) else per_step
+    v = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    if v.ndim != 1 or v.size != num_steps:
+        raise ValueError(f"num_integration_steps_per_step must hold num_steps = {num_steps} counts (got shape {v.shape})")
+    if num_steps and not ((v == np.floor(v)) & (v >= 1) & (v <= 100000)).all():
+        raise ValueError("num_integration_steps_per_step: every count must be an integer in [1, 100000]")
+    return np.ascontiguousarray(v, dtype=np.int32)
+
+
 def _mass_engine(dist, inverse_mass_matrix):
     """The engine of ``dist`` with this call's mass installed on (or cleared from) its context."""
     minv = check_inverse_mass(inverse_mass_matrix, getattr(dist, "dim", None))
@@ -121,10 +146,13 @@ def build_kernel():
         return HMCState(pos, logp, grad), HMCInfo(acc, isacc.bool())
 
     def run(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int, thin: int = 0,
-            inverse_mass_matrix=None):
+            inverse_mass_matrix=None, num_integration_steps_per_step=None):
         """``num_steps`` calls of ``kernel`` in one: with ONE key step j uses ``split(rng_key, num_steps)[j]`` (the scan of
         ``inference_loop0``); with keys ``[n_chain_local, 2]`` step j of chain b uses ``split(rng_key[b], num_steps)[j]``.
-        Bit-identical with that loop.  ``thin >= 1`` keeps the state after every ``thin``-th step."""
+        Bit-identical with that loop.  ``thin >= 1`` keeps the state after every ``thin``-th step.
+        ``num_integration_steps_per_step`` (array-like of ``num_steps`` ints, or a callable ``i -> int``) gives step j its own number of
+        leapfrog steps in place of ``num_integration_steps`` (``mfm_hmc_run_lengths``: the sampler ``chees_adaptation`` adapts)."""
+        lengths = None if num_integration_steps_per_step is None else integration_step_counts(num_integration_steps_per_step, num_steps)
         dist, beta = resolve_logdensity(logdensity_fn)
         eng = _mass_engine(dist, inverse_mass_matrix)
         t = eng.torch
@@ -141,6 +169,11 @@ def build_kernel():
             traj_logp = t.empty((num_steps // thin, n), device=dev, dtype=t.float64)
         if getattr(rng_key, "ndim", 1) == 2:
             rng_key = _device_keys(t, rng_key, dev)
+        if lengths is not None:
+            total = t.zeros(1, device=dev, dtype=t.int64)
+            eng.ctx.hmc_run_lengths(rng_key, beta, step_size, t.as_tensor(lengths, device=dev), pos, logp, grad, thin=thin, n_acc=n_acc,
+                                    acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp, total_leapfrog=total)
+            return HMCState(pos, logp, grad), HMCRunLengthsInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp, int(total.item()))
         eng.ctx.hmc_run(rng_key, beta, step_size, num_integration_steps, num_steps, pos, logp, grad, thin=thin, n_acc=n_acc,
                         acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp)
         return HMCState(pos, logp, grad), HMCRunInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp)
@@ -175,8 +208,8 @@ class hmc:
         def step_fn(rng_key, state):
             return kernel(rng_key, state, logdensity_fn, step_size, num_integration_steps, minv)
 
-        def run_fn(rng_key, state, num_steps, thin=0):
-            return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin, minv)
+        def run_fn(rng_key, state, num_steps, thin=0, num_integration_steps_per_step=None):
+            return kernel.run(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, thin, minv, num_integration_steps_per_step)
 
         def warmup_fn(rng_key, state, num_steps, target_acceptance_rate=0.8, keep_step_sizes=False):
             return kernel.warmup(rng_key, state, logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate, keep_step_sizes, minv)

@@ -19,6 +19,7 @@
 #include "nuts.hip"
 #include "warmup.hip"
 #include "nuts_warmup.hip.h"
+#include "chees.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -109,6 +110,7 @@ struct mfm_ctx {
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* cs_ws = nullptr; size_t cs_ws_cap = 0;     // mfm_chain_sums: mean and A_0 of every sub-chain, then the slabs [n_slices][n_lags + 2][dim] of float64 partial sums
   void* run_ws = nullptr; size_t run_ws_cap = 0;  // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
+  void* chees_ws = nullptr; size_t chees_ws_cap = 0;      // mfm_chees_warmup: the CheesState, the column means, g, and the per-chain records the caller did not pass (chees.hip: CheesBufs)
   void* svgd_ws = nullptr; size_t svgd_ws_cap = 0;        // mfm_svgd_*: column means, centred coordinates, row norms, selection state (svgd.hip: Scratch)
   void* svgd_step_ws = nullptr; size_t svgd_step_ws_cap = 0;   // mfm_svgd_step: D [n][n], the functional gradient, the target's log-density and gradient
   mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
@@ -401,7 +403,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -813,6 +815,79 @@ extern "C" int mfm_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, c
   LAUNCHCHK();
   // steps only, next to mfm_hmc_step's: CTR_MALA_BYTES is the MALA kernels' traffic and covers no HMC entry point
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;
+  return MFM_OK;
+}
+
+// mfm_hmc_run with one leapfrog count per step (chees.hip): mfm_hmc_run's checks in its order, the array in num_steps' place
+extern "C" int mfm_hmc_run_lengths(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step,
+                                   const int32_t* d_num_steps, int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad,
+                                   int32_t* d_n_acc, double* d_acc_sum, float* d_acc, uint8_t* d_isacc, float* d_traj_pos, double* d_traj_logp,
+                                   int64_t* d_total_leapfrog) { use_ctx(x);
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  if (!d_num_steps) return fail(MFM_EINVAL, "d_num_steps must not be null (one leapfrog count per step)");
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  CHECKED(hmc_refuse_cox(x));
+  HmcRunArgs r; memset(&r, 0, sizeof r);
+  r.h = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, 0, d_pos, d_logp, d_grad, d_acc, d_isacc);
+  r.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_hmc_run_lengths(r, d_num_steps, d_total_leapfrog, x->stream)) return too_large(x, "HMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+
+// ChEES-HMC warmup (chees.hip): n_iter iterations of four launches each, enqueued back to back; the host reads nothing until the end
+static size_t chees_align(size_t n) { return (n + 255) & ~(size_t)255; }
+extern "C" int mfm_chees_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, double traj0,
+                                int32_t n_iter, int32_t n_valid, double target_accept, double learning_rate, int32_t max_leapfrog, double decay,
+                                double div_thr, float* d_pos, double* d_logp, float* d_grad, double* h_result, double* d_trace, float* d_prop,
+                                double* d_vel, double* d_alpha) { use_ctx(x);
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step0));
+  CHECKED(check_run_keys(key_mode, d_keys, n_iter));
+  CHECKED(hmc_refuse_cox(x));
+  const int B = x->cfg.n_chain_local, d = x->cfg.dim;
+  if (x->cfg.n_chain_total != B)
+    return fail(MFM_EUNSUPPORTED, "the ChEES warmup serves one rank (n_chain_total %d != n_chain_local %d): the chains' means would need an all-reduce", x->cfg.n_chain_total, B);
+  if (n_valid < 2 || n_valid > B) return fail(MFM_EINVAL, "n_valid must be in [2, n_chain_local = %d] (got %d)", B, n_valid);
+  if (!(traj0 > 0)) return fail(MFM_EINVAL, "trajectory_length must be positive (got %g)", traj0);
+  if (!(learning_rate > 0)) return fail(MFM_EINVAL, "learning_rate must be positive (got %g)", learning_rate);
+  if (!(decay >= 0 && decay < 1)) return fail(MFM_EINVAL, "decay must lie in [0, 1) (got %g)", decay);
+  if (max_leapfrog < 1 || max_leapfrog > 100000) return fail(MFM_EINVAL, "max_leapfrog must be in [1, 100000] (got %d)", max_leapfrog);
+  if (!(target_accept > 0 && target_accept < 1)) return fail(MFM_EINVAL, "target_accept must lie strictly inside (0, 1) (got %g)", target_accept);
+  if (!(div_thr > 0)) return fail(MFM_EINVAL, "divergence_threshold must be positive (got %g)", div_thr);
+  if ((d + 63) / 64 > 32) return too_large(x, "HMC");
+  // workspace: CheesState | mean [2][d] | g [B] | alpha [B] | vel [B][d] | x0 [B][d] | prop [B][d] | div [B]
+  const size_t bd = (size_t)B * d;
+  const size_t o_mean = chees_align(sizeof(CheesState)), o_g = o_mean + chees_align(16 * (size_t)d), o_alpha = o_g + chees_align(8 * (size_t)B),
+               o_vel = o_alpha + chees_align(8 * (size_t)B), o_x0 = o_vel + chees_align(8 * bd), o_prop = o_x0 + chees_align(4 * bd),
+               o_div = o_prop + chees_align(4 * bd), need = o_div + chees_align((size_t)B);
+  if (x->chees_ws_cap < need) {
+    if (x->chees_ws) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(x->chees_ws); x->chees_ws = nullptr; x->chees_ws_cap = 0; }
+    HIPCHK(hipMalloc(&x->chees_ws, need));
+    x->chees_ws_cap = need;
+  }
+  char* ws = (char*)x->chees_ws;
+  CheesBufs c;
+  c.st = (CheesState*)ws; c.mean = (double*)(ws + o_mean); c.g = (double*)(ws + o_g);
+  c.alpha = d_alpha ? d_alpha : (double*)(ws + o_alpha); c.vel = d_vel ? d_vel : (double*)(ws + o_vel);
+  c.x0 = (float*)(ws + o_x0); c.prop = d_prop ? d_prop : (float*)(ws + o_prop); c.div = (uint8_t*)(ws + o_div);
+  c.trace = d_trace;
+  const CheesConst k{n_iter, n_valid, max_leapfrog, target_accept, learning_rate, decay, div_thr};
+  const HmcArgs a = hmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, 0, d_pos, d_logp, d_grad, nullptr, nullptr);
+  ProfScope ps_(x, PROF_MALA);
+  hipLaunchKernelGGL(chees_begin_kernel, dim3(1), dim3(64), 0, x->stream, c.st, step0, traj0, max_leapfrog);
+  for (int t = 0; t < n_iter; ++t)
+    if (launch_chees_iteration(a, c, k, key_mode, x->stream)) return too_large(x, "HMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)B * n_iter;      // (steps only, as mfm_hmc_run)
+  if (h_result) {                                // the call's only read-back, after everything is enqueued
+    HIPCHK(hipMemcpyAsync(h_result, c.st->result, 4 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
+    HIPCHK(hipStreamSynchronize(x->stream));
+  }
   return MFM_OK;
 }
 

@@ -38,6 +38,7 @@ struct HmcInHbm {
   const HmcArgs& a; size_t row; int b;
   __device__ __forceinline__ void element(int it, int j, float& x, float& g) const { x = a.pos[row + j]; g = a.grad[row + j]; }
   __device__ __forceinline__ double logdensity() const { return a.logp[b]; }
+  template <int MAXIT> __device__ __forceinline__ void momentum(const double (&)[MAXIT], double, int, int) const {}      // (hmc_trajectory: for chees.hip's sink)
   // an accepted end point replaces the state; the step's info
   template <int MAXIT> __device__ __forceinline__ void finish(bool acc, double pa, double lp, const float (&x)[MAXIT], const float (&g)[MAXIT], int d, int lane) const {
     if (acc) {
@@ -135,6 +136,7 @@ __device__ __forceinline__ void hmc_trajectory(const TargetDev& T, double beta, 
   const double h1 = -lp + 0.5 * wave_sum(kin1);
   const double pa = mala_accept_p(h0 - h1, dr);
   const bool acc = dr.uniform(k_acc) < pa;
+  st.template momentum<MAXIT>(p, h1 - h0, d, lane);      // the end momentum and H_end - H_0, for a sink that keeps them (chees.hip); empty in the others
   st.template finish<MAXIT>(acc, pa, lp, x, g, d, lane);
 }
 

@@ -31,6 +31,7 @@ template <int MAXIT> struct HmcResident {
   bool acc; double pa;                                   // the step's outcome
   __device__ __forceinline__ void element(int it, int j, float& xo, float& go) const { xo = x[it]; go = g[it]; }
   __device__ __forceinline__ double logdensity() const { return lp; }
+  template <int M> __device__ __forceinline__ void momentum(const double (&)[M], double, int, int) const {}
   template <int M> __device__ __forceinline__ void finish(bool acc_, double pa_, double lpe, const float (&xe)[M], const float (&ge)[M], int d, int lane) {
     const double lpe0 = __shfl(lpe, 0, 64);     // the value a single-step launch stores (lane 0's) and the next one loads in every lane
 #pragma unroll

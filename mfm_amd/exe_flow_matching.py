@@ -239,7 +239,7 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
         elif do_flow:
             eng.ctx.flow_step(mode, rng_key, beta, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["nsteps"])
         elif use_hmc:          # build-side mode (--mcmc_kernel hmc): the iteration's MCMC move is an HMC step (mfm_hmc_step) instead of :313
-            eng.ctx.hmc_step(rng_key, beta, args.step_size, int(args.hmc_steps), pos, logp, grad, info["acc"], info["isacc"])
+            eng.ctx.hmc_step(rng_key, beta, args.step_size, hmc_num_steps(args, count), pos, logp, grad, info["acc"], info["isacc"])
         elif use_nuts:         # build-side mode (--mcmc_kernel nuts): a No-U-turn transition (mfm_nuts_step); it always takes its tree's proposal
             eng.ctx.nuts_step(rng_key, beta, args.step_size, int(getattr(args, "max_tree_depth", 10)), pos, logp, grad, acceptance_rate=info["nuts_acc"])
             info["acc"].copy_(info["nuts_acc"]); info["isacc"].fill_(1)
@@ -369,7 +369,9 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
     if adapt_stats:
         logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']} (mean acceptance probability over the warmup= {adapt_stats['adapt_acceptance']})")
-        if "adapt_mean_leapfrog" in adapt_stats:                                            # (--nuts_adapt tree)
+        if "adapted_trajectory_length" in adapt_stats:                                      # (--hmc_adapt chees)
+            logger.info(f"Adapted trajectory length= {adapt_stats['adapted_trajectory_length']} (mean leapfrog steps per iteration= {adapt_stats['adapt_mean_leapfrog']:.4g})")
+        elif "adapt_mean_leapfrog" in adapt_stats:                                          # (--nuts_adapt tree)
             logger.info(f"NUTS warmup: mean leapfrog steps per transition= {adapt_stats['adapt_mean_leapfrog']:.4g}")
         if "adapted_inverse_mass" in adapt_stats:
             logger.info(f"Adapted inverse mass matrix (diagonal): min= {adapt_stats['adapted_inverse_mass_min']}, max= {adapt_stats['adapted_inverse_mass_max']}")
@@ -454,7 +456,8 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     if ess_stats:
         use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
         use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
-        step_name = f"HMC step ({int(args.hmc_steps)} leapfrog steps)" if use_hmc else "NUTS transition" if use_nuts else "MALA step"
+        step_name = (f"HMC step ({ess_stats['hmc_mean_leapfrog']:.4g} leapfrog steps on average)" if "hmc_mean_leapfrog" in ess_stats
+                     else f"HMC step ({int(args.hmc_steps)} leapfrog steps)") if use_hmc else "NUTS transition" if use_nuts else "MALA step"
         logger.info(f"ESS per {step_name} (min, median, mean over chains and coordinates)= "
                     + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_step_min", "ess_per_step_median", "ess_per_step_mean")))
         if use_nuts:
@@ -494,12 +497,32 @@ def check_adapt_args(args):
     if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") not in ("hmc", "nuts"):
         raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
                          "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
+    hmc_adapt = getattr(args, "hmc_adapt", "dual")
+    if hmc_adapt not in ("dual", "chees"):
+        raise ValueError(f"--hmc_adapt must be dual or chees (got {hmc_adapt!r})")
+    if hmc_adapt == "chees":
+        if getattr(args, "mcmc_kernel", "mala") != "hmc":
+            raise ValueError("--hmc_adapt chees adapts the HMC kernel's step size and trajectory length: it needs --mcmc_kernel hmc")
+        if n_steps == 0:
+            raise ValueError("--hmc_adapt chees runs its iterations during the --adapt_steps N warmup: give N > 0")
+        if getattr(args, "adapt_mass", False):
+            raise ValueError("--hmc_adapt chees uses the mass matrix as given: it does not go with --adapt_mass")
     nuts_adapt = getattr(args, "nuts_adapt", "hmc")
     if nuts_adapt not in ("hmc", "tree"):
         raise ValueError(f"--nuts_adapt must be hmc or tree (got {nuts_adapt!r})")
     if nuts_adapt == "tree" and getattr(args, "mcmc_kernel", "mala") != "nuts":
         raise ValueError("--nuts_adapt tree adapts on the No-U-turn sampler's own trees: it needs --mcmc_kernel nuts")
     return n_steps
+
+
+def hmc_num_steps(args, i):
+    """The leapfrog steps of the HMC step of training iteration / sampling step ``i``: ``--hmc_steps``, or under ``--hmc_adapt chees`` the
+    jittered count ``integration_steps_fn(i)`` of the adapted ``(step_size, hmc_trajectory_length)``."""
+    T = getattr(args, "hmc_trajectory_length", None)
+    if T is None:
+        return int(args.hmc_steps)
+    from .bblackjax.adaptation.chees_adaptation import integration_steps
+    return integration_steps(i, args.step_size, T)
 
 
 def adapt_step_size(eng, dist, args, pos0, key_gen):
@@ -521,12 +544,27 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     the warmup is NUTS's own instead: N transitions under ``--max_tree_depth`` in one launch (``nuts(...).step.warmup``,
     ``mfm_nuts_warmup``), every chain adapting on the mean over its tree's leaves of ``min(1, exp(H0 - H))``; with ``--adapt_mass``
     ``nuts_window_adaptation``.  ``--hmc_steps`` plays no part, and the result also carries ``adapt_mean_leapfrog``, the mean number
-    of leapfrog steps per transition over the warmup (with ``--adapt_mass``: of the last segment)."""
+    of leapfrog steps per transition over the warmup (with ``--adapt_mass``: of the last segment).
+
+    ``--hmc_adapt chees``: the N steps are N ChEES-HMC iterations (``chees_adaptation``, ``mfm_chees_warmup``) on the same key and copy: the
+    chains adapt ONE step size (towards the harmonic-mean acceptance ``--adapt_target``) and ONE trajectory length together.  ``args.step_size`` and ``args.hmc_trajectory_length`` are set, and the
+    HMC step of training iteration i and of ``--ess_steps`` then makes ``hmc_num_steps(args, i)`` leapfrog steps in place of ``--hmc_steps``.
+    The result carries ``adapted_step_size``, ``adapted_trajectory_length``, ``adapt_acceptance`` (the last iteration's harmonic-mean
+    acceptance) and ``adapt_mean_leapfrog`` (the mean leapfrog count over the iterations)."""
     n_steps = check_adapt_args(args)
     if n_steps <= 0:
         return {}
     from .bblackjax.mcmc.hmc import hmc
     from .engine import global_mean_std
+    if getattr(args, "hmc_adapt", "dual") == "chees":
+        from .bblackjax.adaptation.chees_adaptation import chees_adaptation
+        from .bblackjax.optimizers import adam
+        algo = hmc(dist.logprob, args.step_size, 1)
+        (_, params), info = chees_adaptation(dist.logprob, eng.n_valid, float(getattr(args, "adapt_target", 0.8))).run(
+            jr.split(key_gen, 4)[3], algo.init(pos0), args.step_size, adam(0.025), n_steps)
+        args.step_size, args.hmc_trajectory_length = params["step_size"], params["trajectory_length"]
+        return dict(adapted_step_size=params["step_size"], adapted_trajectory_length=params["trajectory_length"],
+                    adapt_acceptance=info.harmonic_mean_acceptance[-1].item(), adapt_mean_leapfrog=info.num_integration_steps.mean().item())
     if getattr(args, "nuts_adapt", "hmc") == "tree":
         from .bblackjax.mcmc.nuts import nuts
         depth, target = int(getattr(args, "max_tree_depth", 10)), float(getattr(args, "adapt_target", 0.8))
@@ -593,11 +631,19 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     else:
         from .bblackjax.mcmc.mala import mala
         algo = mala(dist.logprob, args.step_size)
-    _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1)
+    chees = use_hmc and getattr(args, "hmc_trajectory_length", None) is not None          # (--hmc_adapt chees: the jittered leapfrog counts)
+    if chees:
+        _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1,
+                                num_integration_steps_per_step=lambda i: hmc_num_steps(args, i))
+    else:
+        _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1)
     ess, _ = mcmc_utils.effective_sample_size(info.positions[:, :eng.n_valid], ctx=eng.ctx)
     per_step = (ess.double() / n_steps).reshape(-1)
     out = dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
     grads_per_step = float(int(args.hmc_steps)) if use_hmc else 1.0
+    if chees:          # the measured mean leapfrog count per step (the same for every chain), as NUTS
+        grads_per_step = info.num_leapfrog / n_steps
+        out["hmc_mean_leapfrog"] = grads_per_step
     if use_nuts:       # a transition costs its tree's leapfrog steps: the measured mean over the run's transitions and the chains of all ranks
         from .engine import global_mean_std
         per_chain = torch.stack([info.num_integration_steps.double() / n_steps, info.mean_trajectory_expansions.double(),

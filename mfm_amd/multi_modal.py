@@ -4,7 +4,7 @@ overrides, ``multi_modal.py:21-101,147-220``), running the MFM loop on MI355X.
 Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / ``--force_num_chain`` override the
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
-``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic),
+``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic; ``--hmc_adapt chees``: the N steps are ChEES-HMC iterations, which adapt the step size and the trajectory length across the chains, and the HMC steps then make a jittered number of leapfrog steps in place of ``--hmc_steps``),
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -182,6 +182,10 @@ def build_parser():
     # with --mcmc_kernel nuts --adapt_steps N: 'hmc' runs the HMC warmup with --hmc_steps leapfrog steps and hands its step size (and mass) to
     # NUTS; 'tree' runs NUTS's own warmup under --max_tree_depth, adapting on the trees' acceptance statistic (--hmc_steps plays no part)
     parser.add_argument('--nuts_adapt', type=str, default='hmc', choices=['hmc', 'tree'])
+    # with --mcmc_kernel hmc --adapt_steps N: 'dual' is the per-chain dual-averaging warmup above; 'chees' runs N ChEES-HMC iterations
+    # (bblackjax/adaptation/chees_adaptation.py), which adapt the step size AND the trajectory length across the chains: the HMC steps then
+    # make a jittered number of leapfrog steps in place of --hmc_steps (not with --adapt_mass)
+    parser.add_argument('--hmc_adapt', type=str, default='dual', choices=['dual', 'chees'])
     # the SVGD baseline (exe_others.run_svgd): --learning_iter iterations of Stein variational gradient descent on the initial particles at
     # beta = 1 under the named optimizer (bblackjax/optimizers); cocob is parameter-free and ignores --svgd_step_size
     parser.add_argument('--do_svgd', dest='do_svgd', action='store_true')
