@@ -320,6 +320,46 @@ int mfm_chees_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, c
                      int32_t max_leapfrog, double decay, double divergence_threshold,
                      float* d_pos, double* d_logp, float* d_grad,
                      double* h_result /* [4] */, double* d_trace, float* d_prop, double* d_vel, double* d_alpha);
+/* PARALLEL TEMPERING (replica exchange; pt.hip, tests/pt_ref.py restates it in float64).  n_temps = K temperatures, n_ladders = R
+ * independent ladders: chain b = r * K + k is slot k of ladder r and runs at h_betas[k] with step size h_step_sizes[k]; slot 0 is the one
+ * that is kept (usually h_betas[0] = 1).  K * R <= n_chain_local; rows from K * R on are never read or written.  Both vectors are HOST
+ * arrays of K doubles, which the library uploads itself.
+ * One round t = 0 .. n_rounds - 1 of mfm_pt_run:
+ *   1. n_local local steps of every chain at its own (beta_k, eps_k): HMC steps of num_steps leapfrog steps (kernel 1) or MALA steps
+ *      under mfm_mala_run's textbook flag (kernel 0);
+ *   2. with exchange = 1 one sweep of deterministic even-odd parity (Syed et al. 2019): the pairs (k, k + 1) with k % 2 == t % 2 in every
+ *      ladder; slots without a partner at that parity are untouched.  exchange = 0: no sweep, independent tempered chains.
+ * The exchange of a pair of slots (i, j = i + 1) of one ladder: c_i = the log-density and gradient of x_j at beta_i, c_j = those of x_i
+ * at beta_j, each with the bits mfm_mala_init gives for that position and beta; delta = (c_i + c_j) - (lp_i + lp_j) in float64, every
+ * operation rounded on its own; p = min(1, exp(delta)), a NaN delta rejects; accepted iff u < p.  On accept the two position rows swap,
+ * each slot takes the candidate log-density and gradient evaluated at its own beta (the state mfm_mala_init would give), and the two
+ * entries of d_replica swap.  This is Metropolis on the joint: correct for any tempering path.
+ * KEY SCHEDULE, from the one key: (k_move, k_swap) = split(key, 2).  Round t's local steps are mfm_hmc_run / mfm_mala_run in key_mode 0
+ * on split(k_move, n_rounds)[t] with n_steps = n_local (chain b has the bits of that call at the scalars beta_k, eps_k).  Round t's sweep
+ * runs on split(k_swap, n_rounds)[t]: the pair whose LOWER slot is chain i draws u = uniform of split(that, n_chain_total)[chain_offset + i].
+ * mfm_pt_exchange is one sweep of the given parity on the given key (pair keys as above).
+ * Outputs of mfm_pt_run (each may be NULL; the tallies are zeroed first, the call only enqueues): d_n_accepted int32[K * R] and d_acc_sum
+ * double[K * R], the local steps' accepted count and sum of acceptance probabilities per slot over all rounds; d_replica int32[K * R], IN
+ * and out, which start replica sits in which slot; d_swap_accepted int32[R][K - 1] and d_swap_prob double[R][K - 1], per pair (by its
+ * lower slot) the accepted swaps and the sum of p (mfm_pt_exchange ADDS to both); with thin >= 1 (n_rounds % thin == 0, at least one of
+ * the two pointers) slot 0 of every ladder after the sweep of every round with (t + 1) % thin == 0: d_traj_pos float[n_rounds / thin][R][dim],
+ * d_traj_logp double[n_rounds / thin][R], contiguous as mfm_autocorr / mfm_chain_sums read them.
+ * Checks, in order: the state pointers; kernel in {0, 1}; num_steps as mfm_hmc_run (HMC); the Cox process and an installed inverse mass:
+ * MFM_EUNSUPPORTED; n_chain_total != n_chain_local: MFM_EUNSUPPORTED (one rank only); n_temps in [2, 64]; n_ladders >= 1;
+ * K * R <= n_chain_local; every beta and step size finite and positive; parity in {0, 1} (mfm_pt_exchange); n_local >= 1; n_rounds >= 1;
+ * exchange in {0, 1}; thin as mfm_hmc_run with n_rounds in n_steps' place.  A rejected call touches nothing. */
+int mfm_pt_exchange(mfm_ctx* ctx, uint32_t key0, uint32_t key1, const double* h_betas /* HOST double[n_temps] */,
+                    int32_t n_temps, int32_t n_ladders, int32_t parity,
+                    float* d_pos, double* d_logp, float* d_grad,
+                    int32_t* d_replica, int32_t* d_swap_accepted, double* d_swap_prob);
+int mfm_pt_run(mfm_ctx* ctx, int kernel /* 0 MALA, 1 HMC */, uint32_t key0, uint32_t key1,
+               const double* h_betas, const double* h_step_sizes /* HOST double[n_temps] */,
+               int32_t n_temps, int32_t n_ladders, int32_t num_steps /* leapfrog, HMC */, int textbook /* MALA */,
+               int32_t n_local, int32_t n_rounds, int exchange /* 0 none, 1 even-odd */, int32_t thin,
+               float* d_pos, double* d_logp, float* d_grad,
+               int32_t* d_n_accepted, double* d_acc_sum, int32_t* d_replica,
+               int32_t* d_swap_accepted, double* d_swap_prob,
+               float* d_traj_pos, double* d_traj_logp);
 /* STEP-SIZE WARMUP OF THE NO-U-TURN SAMPLER: n_steps NUTS transitions in ONE launch, as mfm_nuts_run (chain resident in registers,
  * key_mode 0 / 1 and their key schedules, max_tree_depth / divergence_threshold and the installed inverse mass as there), in which every
  * chain adapts its OWN step size by the dual averaging of mfm_hmc_warmup -- the same recursion, constants and clamp, eps_1 = step0

@@ -71,6 +71,9 @@ _SIGS = {
     "mfm_hmc_run_lengths": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_chees_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                    C.c_int32, C.c_double, C.c_double, _P, _P, _P, C.POINTER(C.c_double), _P, _P, _P, _P]),
+    "mfm_pt_exchange": (C.c_int, [_P, _U32, _U32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    "mfm_pt_run": (C.c_int, [_P, C.c_int, _U32, _U32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int,
+                             C.c_int32, C.c_int32, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, _P, _P, _P,
@@ -391,6 +394,52 @@ class Context:
                                        _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), res, _ptr(trace, F64), _ptr(prop, F32),
                                        _ptr(vel, F64), _ptr(alpha, F64)))
         return tuple(res) if read_result else None
+
+    @staticmethod
+    def _host_f64(a, n=None):
+        """A host vector for a ``const double* h_`` argument (kept alive by the caller for the duration of the call)."""
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+        if n is not None and a.size != n:
+            raise MfmError(f"expected {n} values, got {a.size}")
+        return a, a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def pt_exchange(self, key, betas, n_ladders, parity, pos, logp, grad, replica=None, swap_accepted=None, swap_prob=None):
+        """``mfm_pt_exchange``: one exchange sweep of parallel tempering on ``key``: in every one of the ``n_ladders`` ladders of
+        ``len(betas)`` slots the pairs ``(k, k + 1)`` with ``k % 2 == parity`` (chain ``r * K + k`` is slot ``k`` of ladder ``r``); the
+        pair whose lower slot is chain ``i`` draws from ``split(key, n_chain_total)[i]``.  State swapped in place.  Optional device
+        tensors: ``replica`` int32 ``[K * R]``, permuted with the rows; ``swap_accepted`` int32 / ``swap_prob`` float64 ``[R, K - 1]``,
+        ADDED to."""
+        hb, pb = self._host_f64(betas)
+        K, R = hb.size, int(n_ladders)
+        for name, t_, need in (("replica", replica, K * R), ("swap_accepted", swap_accepted, R * (K - 1)), ("swap_prob", swap_prob, R * (K - 1))):
+            if t_ is not None and t_.numel() < need:
+                raise MfmError(f"{name} must hold {need} elements (got {t_.numel()})")
+        _chk(self.lib.mfm_pt_exchange(self.h, int(key[0]), int(key[1]), pb, K, R, int(parity), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                      _ptr(replica, I32), _ptr(swap_accepted, I32), _ptr(swap_prob, F64)))
+
+    def pt_run(self, key, betas, step_sizes, n_ladders, n_local, n_rounds, pos, logp, grad, kernel="hmc", num_steps=10, textbook=False,
+               exchange=True, thin=0, n_acc=None, acc_sum=None, replica=None, swap_accepted=None, swap_prob=None, traj_pos=None,
+               traj_logp=None):
+        """``mfm_pt_run``: ``n_rounds`` rounds of parallel tempering in one call (it only enqueues), state updated in place.  A round is
+        ``n_local`` local steps of every chain at its slot's ``(betas[k], step_sizes[k])`` -- ``kernel`` ``"hmc"`` with ``num_steps``
+        leapfrog steps, or ``"mala"`` under ``textbook`` -- then, with ``exchange``, one even-odd sweep.  The key schedule:
+        ``include/mfm.h``.  Optional device tensors: ``n_acc`` int32 / ``acc_sum`` float64 ``[K * R]`` (per slot, over all rounds);
+        ``replica`` int32 ``[K * R]`` (in and out); ``swap_accepted`` int32 / ``swap_prob`` float64 ``[R, K - 1]``; with ``thin`` slot 0 of
+        every ladder after each kept round: ``traj_pos`` float32 ``[n_rounds / thin, R, dim]``, ``traj_logp`` float64 ``[n_rounds / thin, R]``."""
+        hb, pb = self._host_f64(betas)
+        K, R = hb.size, int(n_ladders)
+        hs, ps = self._host_f64(step_sizes, K)
+        kern = {"mala": 0, "hmc": 1}.get(kernel, kernel)
+        n_keep = max(int(n_rounds), 0) // int(thin) if int(thin) > 0 else 0
+        for name, t_, need in (("n_acc", n_acc, K * R), ("acc_sum", acc_sum, K * R), ("replica", replica, K * R),
+                               ("swap_accepted", swap_accepted, R * (K - 1)), ("swap_prob", swap_prob, R * (K - 1)),
+                               ("traj_pos", traj_pos, n_keep * R * self.dim), ("traj_logp", traj_logp, n_keep * R)):
+            if t_ is not None and t_.numel() < need:
+                raise MfmError(f"{name} must hold {need} elements (got {t_.numel()})")
+        _chk(self.lib.mfm_pt_run(self.h, int(kern), int(key[0]), int(key[1]), pb, ps, K, R, int(num_steps), int(bool(textbook)), int(n_local),
+                                 int(n_rounds), int(bool(exchange)) if not isinstance(exchange, int) else int(exchange), int(thin),
+                                 _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(replica, I32),
+                                 _ptr(swap_accepted, I32), _ptr(swap_prob, F64), _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
 
     def _nuts_info(self, depth, num_leapfrog, is_turning, is_divergent, acceptance_rate, energy):
         return (_ptr(depth, I32), _ptr(num_leapfrog, I32), _ptr(is_turning, U8), _ptr(is_divergent, U8), _ptr(acceptance_rate, F64), _ptr(energy, F64))

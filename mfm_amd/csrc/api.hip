@@ -20,6 +20,7 @@
 #include "warmup.hip"
 #include "nuts_warmup.hip.h"
 #include "chees.hip"
+#include "pt.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -111,6 +112,7 @@ struct mfm_ctx {
   void* cs_ws = nullptr; size_t cs_ws_cap = 0;     // mfm_chain_sums: mean and A_0 of every sub-chain, then the slabs [n_slices][n_lags + 2][dim] of float64 partial sums
   void* run_ws = nullptr; size_t run_ws_cap = 0;  // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
   void* chees_ws = nullptr; size_t chees_ws_cap = 0;      // mfm_chees_warmup: the CheesState, the column means, g, and the per-chain records the caller did not pass (chees.hip: CheesBufs)
+  double* pt_ws = nullptr;                                // mfm_pt_run / mfm_pt_exchange: the ladder, betas then step sizes (pt.hip: PtVec)
   void* svgd_ws = nullptr; size_t svgd_ws_cap = 0;        // mfm_svgd_*: column means, centred coordinates, row norms, selection state (svgd.hip: Scratch)
   void* svgd_step_ws = nullptr; size_t svgd_step_ws_cap = 0;   // mfm_svgd_step: D [n][n], the functional gradient, the target's log-density and gradient
   mutable int64_t wgemm_tally[MFM_WGEMM_COUNT] = {};   // mfm_wide_gemm_tally: launches per instance of wide::launch_gemm (host side)
@@ -403,7 +405,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws, x->pt_ws};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -888,6 +890,109 @@ extern "C" int mfm_chees_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t 
     HIPCHK(hipMemcpyAsync(h_result, c.st->result, 4 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
     HIPCHK(hipStreamSynchronize(x->stream));
   }
+  return MFM_OK;
+}
+
+// Parallel tempering (pt.hip).  The shared checks of the two entry points, in the order the header states; a rejected call touches nothing.
+static int pt_check(mfm_ctx* x, const double* h_betas, const double* h_step_sizes, int32_t n_temps, int32_t n_ladders) {
+  CHECKED(hmc_refuse_cox(x));
+  if (!x->h_inv_mass.empty()) return fail(MFM_EUNSUPPORTED, "parallel tempering runs at unit mass: remove the installed inverse mass (mfm_hmc_set_inverse_mass with n = 0)");
+  const int B = x->cfg.n_chain_local;
+  if (x->cfg.n_chain_total != B)
+    return fail(MFM_EUNSUPPORTED, "parallel tempering serves one rank (n_chain_total %d != n_chain_local %d): a ladder's slots would lie on several ranks", x->cfg.n_chain_total, B);
+  if (n_temps < 2 || n_temps > PT_MAX_TEMPS) return fail(MFM_EINVAL, "n_temps must be in [2, %d] (got %d)", PT_MAX_TEMPS, n_temps);
+  if (n_ladders < 1) return fail(MFM_EINVAL, "n_ladders must be at least 1 (got %d)", n_ladders);
+  if ((int64_t)n_temps * n_ladders > B) return fail(MFM_EINVAL, "n_temps * n_ladders (%d * %d) must not exceed n_chain_local = %d", n_temps, n_ladders, B);
+  if (!h_betas) return fail(MFM_EINVAL, "h_betas must not be null (n_temps host values)");
+  for (int k = 0; k < n_temps; ++k)
+    if (!(std::isfinite(h_betas[k]) && h_betas[k] > 0)) return fail(MFM_EINVAL, "betas[%d] = %g: every beta must be finite and positive", k, h_betas[k]);
+  if (h_step_sizes)
+    for (int k = 0; k < n_temps; ++k)
+      if (!(std::isfinite(h_step_sizes[k]) && h_step_sizes[k] > 0)) return fail(MFM_EINVAL, "step_sizes[%d] = %g: every step_size must be finite and positive", k, h_step_sizes[k]);
+  if ((x->cfg.dim + 63) / 64 > 32) return too_large(x, "parallel tempering");
+  return MFM_OK;
+}
+// the ladder to device memory, stream-ordered behind the launches that still read the previous one (by value: no host buffer outlives the call)
+static int pt_upload(mfm_ctx* x, const double* h_betas, const double* h_step_sizes, int n_temps) {
+  if (!x->pt_ws) HIPCHK(hipMalloc(&x->pt_ws, 2 * PT_MAX_TEMPS * sizeof(double)));
+  PtVec b, e; memset(&b, 0, sizeof b); memset(&e, 0, sizeof e);
+  for (int k = 0; k < n_temps; ++k) { b.v[k] = h_betas[k]; e.v[k] = h_step_sizes ? h_step_sizes[k] : 0.0; }
+  hipLaunchKernelGGL(pt_ladder_kernel, dim3(1), dim3(PT_MAX_TEMPS), 0, x->stream, b, e, n_temps, x->pt_ws);
+  return MFM_OK;
+}
+static int pt_sweep(mfm_ctx* x, Key2 key, int K, int R, int parity, float* d_pos, double* d_logp, float* d_grad, int32_t* d_replica,
+                    int32_t* d_swap_acc, double* d_swap_prob) {
+  const int pairs = (K - parity) / 2;
+  MalaArgs a = mala_args(x, 1.0);
+  a.B = pairs * R;
+  const PtSwap s{x->pt_ws, K, parity, pairs, key, (uint32_t)x->cfg.n_chain_total, (uint32_t)x->cfg.chain_offset, d_pos, d_logp, d_grad, d_replica, d_swap_acc, d_swap_prob};
+  return launch_pt_exchange(a, s, x->stream);
+}
+
+extern "C" int mfm_pt_exchange(mfm_ctx* x, uint32_t k0, uint32_t k1, const double* h_betas, int32_t n_temps, int32_t n_ladders, int32_t parity,
+                               float* d_pos, double* d_logp, float* d_grad, int32_t* d_replica, int32_t* d_swap_acc, double* d_swap_prob) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(pt_check(x, h_betas, nullptr, n_temps, n_ladders));
+  if (parity != 0 && parity != 1) return fail(MFM_EINVAL, "parity must be 0 or 1 (got %d)", parity);
+  CHECKED(pt_upload(x, h_betas, nullptr, n_temps));
+  ProfScope ps_(x, PROF_MALA);
+  if (pt_sweep(x, Key2{k0, k1}, n_temps, n_ladders, parity, d_pos, d_logp, d_grad, d_replica, d_swap_acc, d_swap_prob)) return too_large(x, "parallel tempering");
+  LAUNCHCHK();
+  return MFM_OK;
+}
+
+extern "C" int mfm_pt_run(mfm_ctx* x, int kernel, uint32_t k0, uint32_t k1, const double* h_betas, const double* h_step_sizes, int32_t n_temps,
+                          int32_t n_ladders, int32_t num_steps, int textbook, int32_t n_local, int32_t n_rounds, int exchange, int32_t thin,
+                          float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum, int32_t* d_replica,
+                          int32_t* d_swap_acc, double* d_swap_prob, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad) return fail(MFM_EINVAL, "null device pointer");
+  if (kernel != 0 && kernel != 1) return fail(MFM_EINVAL, "kernel must be 0 (MALA) or 1 (HMC) (got %d)", kernel);
+  if (kernel == 1) CHECKED(check_num_steps(num_steps));
+  if (!h_step_sizes) return fail(MFM_EINVAL, "h_step_sizes must not be null (n_temps host values)");
+  CHECKED(pt_check(x, h_betas, h_step_sizes, n_temps, n_ladders));
+  if (n_local < 1) return fail(MFM_EINVAL, "n_local must be at least 1 (got %d)", n_local);
+  if (n_rounds < 1) return fail(MFM_EINVAL, "n_rounds must be at least 1 (got %d)", n_rounds);
+  if (exchange != 0 && exchange != 1) return fail(MFM_EINVAL, "exchange must be 0 (none) or 1 (even-odd) (got %d)", exchange);
+  CHECKED(check_thin(thin, n_rounds, d_traj_pos, d_traj_logp));
+  const int K = n_temps, R = n_ladders, d = x->cfg.dim;
+  const int BK = K * R;
+  CHECKED(pt_upload(x, h_betas, h_step_sizes, K));
+  if (d_n_acc) HIPCHK(hipMemsetAsync(d_n_acc, 0, (size_t)BK * sizeof(int32_t), x->stream));
+  if (d_acc_sum) HIPCHK(hipMemsetAsync(d_acc_sum, 0, (size_t)BK * sizeof(double), x->stream));
+  if (d_swap_acc) HIPCHK(hipMemsetAsync(d_swap_acc, 0, (size_t)R * (K - 1) * sizeof(int32_t), x->stream));
+  if (d_swap_prob) HIPCHK(hipMemsetAsync(d_swap_prob, 0, (size_t)R * (K - 1) * sizeof(double), x->stream));
+  const Key2 k_move = split_at(Key2{k0, k1}, 2, 0), k_swap = split_at(Key2{k0, k1}, 2, 1);
+  const PtLocal p{x->pt_ws, x->pt_ws + PT_MAX_TEMPS, K, d_n_acc, d_acc_sum};
+  ProfScope ps_(x, PROF_MALA);
+  for (int t = 0; t < n_rounds; ++t) {
+    const Key2 km = split_at(k_move, (uint32_t)n_rounds, (uint32_t)t);
+    int rc;
+    if (kernel == 1) {
+      HmcRunArgs r; memset(&r, 0, sizeof r);
+      r.h = hmc_args(x, km.k0, km.k1, nullptr, 1.0, 1.0, num_steps, d_pos, d_logp, d_grad, nullptr, nullptr);
+      r.h.B = BK; r.h.minv = nullptr;
+      r.t = RunTail{0, n_local, 0, nullptr, nullptr, nullptr, nullptr};
+      rc = launch_pt_hmc_run(r, p, x->stream);
+    } else {
+      MalaRunArgs r; memset(&r, 0, sizeof r);
+      r.m = mala_run_args(x, 0, km.k0, km.k1, nullptr, 1.0, 1.0, textbook, d_pos, d_logp, d_grad);
+      r.m.B = BK;
+      r.t = RunTail{0, n_local, 0, nullptr, nullptr, nullptr, nullptr};
+      rc = launch_pt_mala_run(r, p, x->stream);
+    }
+    if (rc) return too_large(x, "parallel tempering");
+    if (exchange && pt_sweep(x, split_at(k_swap, (uint32_t)n_rounds, (uint32_t)t), K, R, t & 1, d_pos, d_logp, d_grad, d_replica, d_swap_acc, d_swap_prob))
+      return too_large(x, "parallel tempering");
+    if (thin > 0 && (t + 1) % thin == 0) {
+      const size_t snap = (size_t)((t + 1) / thin - 1);
+      hipLaunchKernelGGL(pt_traj_kernel, dim3(R), dim3(256), 0, x->stream, d_pos, d_logp, K, R, d,
+                         d_traj_pos ? d_traj_pos + snap * (size_t)R * d : nullptr, d_traj_logp ? d_traj_logp + snap * (size_t)R : nullptr);
+    }
+    LAUNCHCHK();
+  }
+  x->ctr[CTR_MALA] += (int64_t)BK * n_local * n_rounds;      // (steps only, as mfm_hmc_run)
   return MFM_OK;
 }
 

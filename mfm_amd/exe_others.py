@@ -27,6 +27,8 @@ logger = logging.getLogger(__name__)
 def run(dist, args, target_gn=None, return_extras=False):
     import torch
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO)
+    if getattr(args, "do_pt", False):
+        return run_pt(dist, args, target_gn, return_extras)
     if getattr(args, "do_svgd", False) and not getattr(args, "do_smc", False):
         return run_svgd(dist, args, target_gn, return_extras)
     if not getattr(args, "do_smc", False):
@@ -129,5 +131,81 @@ def run_svgd(dist, args, target_gn=None, return_extras=False):
     wandb.finish()
     if return_extras:
         return res, res_, dict(length_scales=length_scales, state=state, engine=eng, samples=particles)
+    eng.close()
+    return res, res_
+
+
+def check_pt_args(args):
+    """``--do_pt``'s argument checks, before any device work: ``(K, R)``."""
+    K = int(getattr(args, "pt_temps", 8))
+    if getattr(args, "do_smc", False) or getattr(args, "do_svgd", False):
+        raise ValueError("--do_pt runs alone: not with --do_smc or --do_svgd")
+    kern = getattr(args, "mcmc_kernel", "mala")
+    if kern not in ("mala", "hmc"):
+        raise ValueError(f"--do_pt takes --mcmc_kernel mala or hmc as the local move (got {kern}: NUTS is not served)")
+    if K < 2 or int(args.num_chain) % K:
+        raise ValueError(f"--do_pt: num_chain ({args.num_chain}) must be a multiple of --pt_temps ({K} >= 2): chains are R ladders of K temperatures")
+    return K, int(args.num_chain) // K
+
+
+def run_pt(dist, args, target_gn=None, return_extras=False):
+    """``--do_pt``: parallel tempering (``bblackjax/mcmc/parallel_tempering.py``) on ``num_chain = R * K`` chains, ``K = --pt_temps``
+    geometric temperatures from 1 to ``--pt_beta_min``, ``--pt_local_steps`` local steps of ``--mcmc_kernel`` (``mala`` under the textbook
+    rule, or ``hmc`` with ``--hmc_steps``) per round at ``--step_size / sqrt(beta_k)``.  ``learning_iter`` rounds, timed as the train
+    time, then ``eval_iter`` rounds with ``thin=1`` whose slot-0 draws give ``res[5]`` in ``--do_smc``'s shape."""
+    import torch
+    from . import diagnostics
+    from .bblackjax.mcmc import parallel_tempering as PT
+    K, R = check_pt_args(args)
+    learning_iter, n_iter, n_chain = int(args.learning_iter), int(args.eval_iter), int(args.num_chain)
+    key_target, key_sample, key_init, key_dist, key_fourier, key_gen = jr.split(jr.PRNGKey(args.seed), 6)     # :33
+    dist.initialize_model(key_dist, n_chain)                                                # :34
+    eng = Engine(dist, args, None, max_eval_samples=max(n_iter * R, 16))
+    if eng.world > 1 or eng.n_valid != eng.n_local:
+        eng.close()
+        raise NotImplementedError("the parallel-tempering baseline runs on one rank with num_chain a multiple of 16 (mfm_pt_run refuses a sharded context)")
+    real_samples = None
+    if target_gn is not None:                                                               # :36-39
+        key_gen, key_loss = jr.split(key_target)
+        real_samples = torch.as_tensor(np.ascontiguousarray(dist.sample_rows(jr.split(key_gen, n_iter * R)), dtype=np.float32), device=eng.dev)
+    betas = PT.geometric_ladder(K, float(getattr(args, "pt_beta_min", 0.01)))
+    kern = getattr(args, "mcmc_kernel", "mala")
+    logger.info(f"===== Starting training seed {args.seed} w/ {learning_iter} iterations =====")
+    logger.info(f"Parallel tempering: {R} ladders of {K} temperatures, beta_min {betas[-1]:g}, local move {kern}")
+    algo = PT.parallel_tempering(dist.logprior, dist.loglik, betas, mcmc=kern, step_size=float(args.step_size),
+                                 num_integration_steps=int(getattr(args, "hmc_steps", 10)), num_mcmc_steps=int(getattr(args, "pt_local_steps", 4)),
+                                 textbook=True)
+    state = algo.init(eng.local(dist.init_params))
+    k_train, k_eval = jr.split(key_sample)
+    train_start = time.time()
+    state, info = algo.step.run(k_train, state, learning_iter)
+    eng.ctx.sync()
+    train_time = time.time() - train_start
+    state, einfo = algo.step.run(k_eval, state, n_iter, thin=1)
+    rates = einfo.swap_acceptance_rate.cpu().numpy() if n_iter > 1 else info.swap_acceptance_rate.cpu().numpy()
+    train_rates = info.swap_acceptance_rate.cpu().numpy()
+    barrier = PT.communication_barrier(np.nan_to_num(train_rates, nan=1.0))
+    logger.info("Swap acceptance rate per pair (training rounds)= " + ", ".join(f"{r:.3f}" for r in train_rates))
+    logger.info(f"Communication barrier= {barrier:.4g}")
+    stats = {"pt_barrier": barrier, **{f"pt_swap_rate_{k}": float(r) for k, r in enumerate(train_rates)}}
+    if n_iter >= 4:
+        cd = diagnostics.chain_diagnostics(einfo.positions, ctx=eng.ctx)
+        rhat, multi = cd.rhat.double(), cd.ess.double() / (float(R) * n_iter)
+        stats.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item(), ess_multichain_per_step_min=multi.min().item(),
+                     ess_multichain_per_step_median=multi.median().item(), ess_multichain_per_step_mean=multi.mean().item())
+        logger.info(f"Split R-hat of slot 0 across ladders (max, median over coordinates)= {stats['rhat_max']:.4g}, {stats['rhat_median']:.4g}")
+        logger.info("Multi-chain ESS per round and ladder (min, median, mean over coordinates)= "
+                    + ", ".join(f"{stats['ess_multichain_per_step_' + k]:.4g}" for k in ("min", "median", "mean")))
+    flow_samples = einfo.positions.reshape(-1, einfo.positions.shape[-1]).contiguous()       # slot 0's draws ("not really flow but MCMC")
+    logpdf = _logprob_any(eng, flow_samples).mean().item()
+    stein = stein_disc(eng, flow_samples)
+    mmd = eng.ctx.max_mean_disc(real_samples, flow_samples) if real_samples is not None else 0.0
+    wandb.log({"train_time": train_time, "logpdf": logpdf, "KSD U-stat": stein[0], "KSD V-stat": stein[1], **stats})
+    res = np.array([logpdf, stein[0], stein[1], mmd, train_time])
+    res_ = res.copy()                                                                       # same particles, as the SMC baseline (:108-109)
+    wandb.finish()
+    if return_extras:
+        return res, res_, dict(state=state, engine=eng, samples=flow_samples, betas=betas, swap_rates=train_rates, eval_swap_rates=rates,
+                               acceptance_rate=info.acceptance_rate, stats=stats)
     eng.close()
     return res, res_

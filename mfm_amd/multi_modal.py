@@ -76,7 +76,11 @@ def main(args):
 
     N_PARAM = args.dim
     job_type = "mcmc_per_flow_steps=" + str(args.mcmc_per_flow_steps) + ",learning_iter=" + str(args.learning_iter) + (",hutchs" if args.hutchs else "")
-    if args.do_smc:
+    if getattr(args, "do_pt", False):
+        from .exe_others import check_pt_args
+        check_pt_args(args)                                                             # (before any device work)
+        job_type = "Parallel tempering"
+    elif args.do_smc:
         job_type = "Adaptive tempered SMC"                                              # :110-111
     elif args.do_svgd:
         job_type = "SVGD"
@@ -85,7 +89,7 @@ def main(args):
     for seed in seeds:
         args.seed = seed
         wandb.init(project=args.example, config=args, group="dim=" + str(N_PARAM), job_type=job_type)
-        if args.do_smc or args.do_svgd:
+        if args.do_smc or args.do_svgd or getattr(args, "do_pt", False):
             _res, _res_ = run_others(dist, args, dist.sample_model)                     # :126-127
         else:
             _res, _res_ = run(dist, args, dist.sample_model, log_every=args.log_every)  # :129
@@ -192,6 +196,13 @@ def build_parser():
     parser.set_defaults(do_svgd=False)
     parser.add_argument('--svgd_optimizer', type=str, default='adagrad', choices=['sgd', 'adagrad', 'adam', 'cocob'])
     parser.add_argument('--svgd_step_size', type=float, default=0.1)
+    # the parallel-tempering baseline (exe_others.run_pt): num_chain = R ladders x --pt_temps temperatures, geometric from 1 to --pt_beta_min,
+    # --pt_local_steps local steps of --mcmc_kernel mala|hmc (--hmc_steps, --step_size / sqrt(beta)) per round, then one even-odd exchange sweep
+    parser.add_argument('--do_pt', dest='do_pt', action='store_true')
+    parser.set_defaults(do_pt=False)
+    parser.add_argument('--pt_temps', type=int, default=8)
+    parser.add_argument('--pt_beta_min', type=float, default=0.01)
+    parser.add_argument('--pt_local_steps', type=int, default=4)
     return parser
 
 
