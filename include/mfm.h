@@ -360,6 +360,50 @@ int mfm_pt_run(mfm_ctx* ctx, int kernel /* 0 MALA, 1 HMC */, uint32_t key0, uint
                int32_t* d_n_accepted, double* d_acc_sum, int32_t* d_replica,
                int32_t* d_swap_accepted, double* d_swap_prob,
                float* d_traj_pos, double* d_traj_logp);
+/* ELLIPTICAL SLICE SAMPLING for the Cox process (Murray, Adams & MacKay 2010; eslice.hip, tests/eslice_ref.py restates it in float64):
+ * BUILD-SIDE MODE like the HMC entry points.  It is the reference's bblackjax/mcmc/tess.py under the linear transport T(u) = mu + L u,
+ * L the Cholesky factor of the prior covariance: the log-det is constant and |u|^2 + |m|^2 is constant on the ellipse, so the slice test
+ * of tess.py:42-44 compares log-likelihoods alone.  No step size, no gradient, every transition moves.  The state of chain b is its
+ * position d_pos float[B][dim] and its UNTEMPERED log-likelihood d_loglik double[B], ll(x) = sum_i (x_i c_i - a exp(x_i)).
+ * One transition at inverse temperature beta (finite, >= 0; beta = 0 accepts the first proposal: an exact prior-preserving rotation):
+ *   1. k_b: the chain's key exactly as mfm_mala_step / mfm_mala_step_keys derive it; (k_nu, k_u, k_theta, k_shrink) = split(k_b, 4);
+ *   2. nu = L n with n = normal(k_nu, (dim,));                       3. log y = beta * ll(x) + log(uniform(k_u));
+ *   4. theta = 2 pi * uniform(k_theta) (float64), lo = theta - 2 pi, hi = theta;
+ *   5. evaluation subiter = 1, 2, ...: x' = mu + (x - mu) cos(theta) + nu sin(theta), accepted when beta * ll(x') is finite and > log y;
+ *      otherwise theta < 0 ? lo = theta : hi = theta, theta = lo + (hi - lo) * uniform(k_shrink, (MFM_ESLICE_MAX_SUBITER,))[subiter - 1];
+ *   6. after MFM_ESLICE_MAX_SUBITER evaluations the chain keeps x and ll(x) (inside the slice by construction) and counts as capped:
+ *      a non-finite position ends at the cap, it does not spin.
+ * mfm_set_lgcp_chol installs L (HOST double[dim * dim], row-major, lower triangular) on a context whose target is the Cox process; a call
+ * of its own like mfm_hmc_set_inverse_mass.  MFM_EUNSUPPORTED for another target (MFM_ENOTARGET without one); MFM_EINVAL for a
+ * non-finite entry or a non-zero entry above the diagonal; a rejected call keeps what was installed.  mfm_set_target removes the factor.
+ * mfm_eslice_init: d_loglik = ll of every row of d_pos.
+ * mfm_eslice_step / _step_keys: one transition, state in place.  Info of the transition (each may be NULL): d_subiter int32[B], the
+ * evaluations made; d_theta double[B], the last angle evaluated (the accepted one unless capped); d_momentum float[B][dim], nu.
+ * mfm_eslice_run: n_steps transitions in ONE launch, the tile's rows resident in registers (a tile of 16 chains never depends on
+ * another), bit-identical with n_steps single-step calls: key_mode 0 / 1, their key schedules, thin and the trajectory layout are
+ * mfm_mala_run's (d_traj_pos float[n_steps / thin][B][dim], d_traj_loglik double[n_steps / thin][B]), so mfm_autocorr and
+ * mfm_chain_sums read the trajectory.  d_subiter_sum int32[B]: the evaluations of all transitions; d_n_capped int32[B]: the capped
+ * transitions; d_subiter_max int32[B]: the most evaluations any one transition made; d_subiter / d_theta / d_momentum take the LAST transition's info, as mfm_mala_run's info arrays do (each may be NULL).
+ * Checks, in mfm_mala_run's order: the state pointers; key_mode / d_keys / n_steps; thin; then a target other than the Cox process:
+ * MFM_EUNSUPPORTED (no Gaussian prior factor); no installed factor: MFM_ENOTARGET; beta not finite or negative: MFM_EINVAL;
+ * n_chain_local not a multiple of 16: MFM_EINVAL; dim beyond the instances (dim > 1664; the largest serves the 40 x 40 grid of the reference's default, dim 1600): MFM_ETOOLARGE.  A rejected call
+ * touches nothing; the calls only enqueue.  A sharded context (n_chain_total, chain_offset) is served: the chains are independent.
+ * mfm_eslice_launch_plan (host only, no context): *h_tpw, the column tiles per wave of the kernel instance that serves dim (1, 2, 4, 8
+ * or 13), and *h_lds_bytes, the dynamic LDS of one workgroup. */
+#define MFM_ESLICE_MAX_SUBITER 64
+int mfm_set_lgcp_chol(mfm_ctx* ctx, const double* h_chol /* HOST [dim * dim], row-major, lower */);
+int mfm_eslice_init(mfm_ctx* ctx, const float* d_pos, double* d_loglik);
+int mfm_eslice_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, float* d_pos, double* d_loglik,
+                    int32_t* d_subiter, double* d_theta, float* d_momentum);
+int mfm_eslice_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, float* d_pos, double* d_loglik,
+                         int32_t* d_subiter, double* d_theta, float* d_momentum);
+int mfm_eslice_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                   double beta, int32_t n_steps, int32_t thin,
+                   float* d_pos, double* d_loglik, int32_t* d_subiter_sum, int32_t* d_n_capped,
+                   float* d_traj_pos, double* d_traj_loglik,
+                   int32_t* d_subiter, double* d_theta, float* d_momentum /* the LAST transition's info, as mfm_eslice_step's */,
+                   int32_t* d_subiter_max);
+int mfm_eslice_launch_plan(int32_t dim, int32_t* h_tpw, int32_t* h_lds_bytes);
 /* STEP-SIZE WARMUP OF THE NO-U-TURN SAMPLER: n_steps NUTS transitions in ONE launch, as mfm_nuts_run (chain resident in registers,
  * key_mode 0 / 1 and their key schedules, max_tree_depth / divergence_threshold and the installed inverse mass as there), in which every
  * chain adapts its OWN step size by the dual averaging of mfm_hmc_warmup -- the same recursion, constants and clamp, eps_1 = step0

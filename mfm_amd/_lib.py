@@ -74,6 +74,12 @@ _SIGS = {
     "mfm_pt_exchange": (C.c_int, [_P, _U32, _U32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "mfm_pt_run": (C.c_int, [_P, C.c_int, _U32, _U32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, C.c_int,
                              C.c_int32, C.c_int32, C.c_int, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_set_lgcp_chol": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "mfm_eslice_init": (C.c_int, [_P, _P, _P]),
+    "mfm_eslice_step": (C.c_int, [_P, _U32, _U32, C.c_double, _P, _P, _P, _P, _P]),
+    "mfm_eslice_step_keys": (C.c_int, [_P, _P, C.c_double, _P, _P, _P, _P, _P]),
+    "mfm_eslice_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_eslice_launch_plan": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mfm_nuts_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, _P, _P, _P,
@@ -207,6 +213,17 @@ def nuts_launch_plan(dim, max_tree_depth):
     return w.value, sm.value, per_cu.value
 
 
+ESLICE_MAX_SUBITER = 64      # include/mfm.h: MFM_ESLICE_MAX_SUBITER
+
+
+def eslice_launch_plan(dim):
+    """``mfm_eslice_launch_plan`` (host only): ``(column tiles per wave of the kernel instance, LDS bytes per workgroup)`` of the
+    elliptical slice kernel at ``dim``."""
+    tpw, sm = C.c_int32(), C.c_int32()
+    _chk(load().mfm_eslice_launch_plan(int(dim), C.byref(tpw), C.byref(sm)))
+    return tpw.value, sm.value
+
+
 WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2     # mfm_wgrad_info: kind
 
 # include/mfm.h: MFM_WGEMM_* (the instances of the wide family's GEMM, in enum order) and MFM_WGEMM_SW_* (its latched switches)
@@ -333,6 +350,38 @@ class Context:
                                    int(textbook), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                    _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8), _ptr(proposed, F32),
                                    _ptr(weight, F32), _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    # ---- elliptical slice sampling for the Cox process (include/mfm.h: mfm_eslice_*) ----
+    def set_lgcp_chol(self, chol):
+        """``mfm_set_lgcp_chol``: install the lower Cholesky factor ``chol [dim, dim]`` (float64, host) of the Cox process prior."""
+        L = np.ascontiguousarray(chol, dtype=np.float64)
+        if L.shape != (self.dim, self.dim):
+            raise MfmError(f"chol must be [{self.dim}, {self.dim}], got {L.shape}")
+        _chk(self.lib.mfm_set_lgcp_chol(self.h, L.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def eslice_init(self, pos, loglik):
+        _chk(self.lib.mfm_eslice_init(self.h, _ptr(pos, F32), _ptr(loglik, F64)))
+
+    def eslice_step(self, key, beta, pos, loglik, subiter=None, theta=None, momentum=None):
+        """``mfm_eslice_step``: one elliptical slice transition of every local chain, state ``(pos, loglik)`` updated in place."""
+        _chk(self.lib.mfm_eslice_step(self.h, int(key[0]), int(key[1]), float(beta), _ptr(pos, F32), _ptr(loglik, F64),
+                                      _ptr(subiter, I32), _ptr(theta, F64), _ptr(momentum, F32)))
+
+    def eslice_step_keys(self, keys, beta, pos, loglik, subiter=None, theta=None, momentum=None):
+        """The same transition on the caller's own keys, an int32/uint32 device tensor ``[n_chain_local, 2]``."""
+        _chk(self.lib.mfm_eslice_step_keys(self.h, _ptr(keys, I32), float(beta), _ptr(pos, F32), _ptr(loglik, F64),
+                                           _ptr(subiter, I32), _ptr(theta, F64), _ptr(momentum, F32)))
+
+    def eslice_run(self, key, beta, n_steps, pos, loglik, thin=0, subiter_sum=None, n_capped=None, traj_pos=None, traj_loglik=None,
+                   subiter=None, theta=None, momentum=None, subiter_max=None, key_mode=None):
+        """``mfm_eslice_run``: ``n_steps`` transitions in one launch, state updated in place; ``key`` and ``key_mode`` as ``mala_run``'s;
+        ``subiter`` / ``theta`` / ``momentum`` take the last transition's info, ``subiter_max`` the most evaluations of any one transition."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_eslice_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), int(n_steps), int(thin),
+                                     _ptr(pos, F32), _ptr(loglik, F64), _ptr(subiter_sum, I32), _ptr(n_capped, I32),
+                                     _ptr(traj_pos, F32), _ptr(traj_loglik, F64), _ptr(subiter, I32), _ptr(theta, F64), _ptr(momentum, F32), _ptr(subiter_max, I32)))
 
     def hmc_step(self, key, beta, step_size, num_steps, pos, logp, grad, acc=None, is_acc=None):
         """Build-side mode (``mfm_hmc_step``): one HMC step of every local chain, state updated in place."""

@@ -1,1 +1,2 @@
 from . import nuts  # noqa: F401
+from . import elliptical_slice  # noqa: F401

@@ -21,6 +21,7 @@
 #include "nuts_warmup.hip.h"
 #include "chees.hip"
 #include "pt.hip"
+#include "eslice.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -120,6 +121,7 @@ struct mfm_ctx {
   // ones when none is set (mfm_hmc_warmup_window runs the mass instances either way); h_inv_mass is the host copy, empty when none is set
   double* d_inv_mass = nullptr;
   std::vector<double> h_inv_mass;
+  float* lgcp_chol = nullptr;      // mfm_set_lgcp_chol: L^T of the Cox process prior, packed as Kinv is (null: none installed)
 };
 
 // The development switches (common.hip.h) are read once per mfm_create and belong to THAT context: every entry point installs its
@@ -405,7 +407,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws, x->pt_ws};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws, x->pt_ws, x->lgcp_chol};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -430,6 +432,7 @@ extern "C" int mfm_set_target(mfm_ctx* x, int kind, const double* p, size_t np) 
   if (!x || !p) return fail(MFM_EINVAL, "null argument");
   TargetDev& T = x->net.T;
   const int d = x->cfg.dim;
+  if (x->lgcp_chol) { (void)hipFree(x->lgcp_chol); x->lgcp_chol = nullptr; }      // the factor belongs to the target it was installed on
   memset(&T, 0, sizeof T);
   T.kind = kind; T.dim = d;
   if (kind == MFM_PHI4) {
@@ -720,6 +723,106 @@ extern "C" int mfm_mala_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, 
   // state in and out once, the trajectory rows that were kept
   x->ctr[CTR_MALA] += (int64_t)B * n_steps;
   x->ctr[CTR_MALA_BYTES] += (int64_t)B * 4 * (4 * d + 4) + (thin > 0 ? (int64_t)(n_steps / thin) * B * (4 * (d_traj_pos ? d : 0) + (d_traj_logp ? 8 : 0)) : 0);
+  return MFM_OK;
+}
+
+// ---- elliptical slice sampling for the Cox process (eslice.hip) ----
+// L of the prior covariance K = L L^T, packed transposed like K^-1 (mfm_set_target): nu = n . L^T is the tile GEMM's product
+extern "C" int mfm_set_lgcp_chol(mfm_ctx* x, const double* h_chol) { use_ctx(x);
+  NEED_TARGET();
+  if (!h_chol) return fail(MFM_EINVAL, "null argument");
+  if (x->net.T.kind != MFM_TARGET_LGCP) return fail(MFM_EUNSUPPORTED, "the Cholesky factor belongs to the Cox process: this target has no Gaussian prior factor");
+  const int d = x->cfg.dim, dp = x->net.dp, KB = dp / 16;
+  for (int j = 0; j < d; ++j)
+    for (int k = 0; k < d; ++k) {
+      const double v = h_chol[(size_t)j * d + k];
+      if (!std::isfinite(v)) return fail(MFM_EINVAL, "chol[%d][%d] = %g: every entry must be finite", j, k, v);
+      if (k > j && v != 0.0) return fail(MFM_EINVAL, "chol[%d][%d] = %g: the factor must be lower triangular", j, k, v);
+    }
+  std::vector<float> lp((size_t)dp * dp, 0.f);
+  for (int j = 0; j < d; ++j)
+    for (int k = 0; k <= j; ++k) lp[pack_index(k, j, KB)] = (float)h_chol[(size_t)j * d + k];      // W[k][j] = L^T[k][j] = L[j][k]
+  if (!x->lgcp_chol) ALLOC(x->lgcp_chol, (size_t)dp * dp);
+  // stream-ordered behind the launches that still read the previous factor; the host vector is a temporary: wait
+  HIPCHK(hipMemcpyAsync(x->lgcp_chol, lp.data(), (size_t)dp * dp * 4, hipMemcpyHostToDevice, x->stream));
+  HIPCHK(hipStreamSynchronize(x->stream));
+  return MFM_OK;
+}
+
+static EsliceArgs eslice_args(mfm_ctx* x, int mode, double beta) {
+  EsliceArgs e; memset(&e, 0, sizeof e);
+  e.T = x->net.T; e.dp = x->net.dp; e.cholP = x->lgcp_chol; e.mode = mode;
+  e.n_total = x->cfg.n_chain_total; e.chain_offset = x->cfg.chain_offset; e.B = x->cfg.n_chain_local; e.beta = beta; e.n_steps = 1;
+  return e;
+}
+// the checks every transition entry point makes after its own (the state pointers first, as mfm_mala_run)
+static int check_eslice(mfm_ctx* x, double beta, bool need_chol) {
+  if (x->net.T.kind != MFM_TARGET_LGCP)
+    return fail(MFM_EUNSUPPORTED, "elliptical slice sampling serves the Cox process: this target has no Gaussian prior factor");
+  if (need_chol && !x->lgcp_chol) return fail(MFM_ENOTARGET, "mfm_set_lgcp_chol has not been called");
+  if (!(std::isfinite(beta) && beta >= 0)) return fail(MFM_EINVAL, "beta must be finite and not negative (got %g)", beta);
+  if (x->cfg.n_chain_local % 16) return fail(MFM_EINVAL, "n_chain_local (%d) must be a multiple of 16 (one tile of 16 chains per workgroup)", x->cfg.n_chain_local);
+  return MFM_OK;
+}
+extern "C" int mfm_eslice_init(mfm_ctx* x, const float* d_pos, double* d_loglik) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_loglik) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_eslice(x, 0.0, false));
+  EsliceArgs e = eslice_args(x, 0, 0.0);
+  e.pos = const_cast<float*>(d_pos); e.loglik = d_loglik;
+  if (launch_eslice(e, x->stream)) return too_large(x, "elliptical slice");
+  LAUNCHCHK();
+  return MFM_OK;
+}
+static int eslice_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, float* d_pos, double* d_loglik,
+                              int32_t* d_subiter, double* d_theta, float* d_momentum) {
+  NEED_TARGET();
+  if (!d_pos || !d_loglik) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_eslice(x, beta, true));
+  EsliceArgs e = eslice_args(x, 1, beta);
+  e.key = Key2{k0, k1}; e.keys = d_keys;
+  e.pos = d_pos; e.loglik = d_loglik; e.subiter = d_subiter; e.theta = d_theta; e.momentum = d_momentum;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_eslice(e, x->stream)) return too_large(x, "elliptical slice");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += x->cfg.n_chain_local;
+  return MFM_OK;
+}
+extern "C" int mfm_eslice_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, float* d_pos, double* d_loglik,
+                               int32_t* d_subiter, double* d_theta, float* d_momentum) { use_ctx(x);
+  return eslice_step_common(x, k0, k1, nullptr, beta, d_pos, d_loglik, d_subiter, d_theta, d_momentum);
+}
+extern "C" int mfm_eslice_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, float* d_pos, double* d_loglik,
+                                    int32_t* d_subiter, double* d_theta, float* d_momentum) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return eslice_step_common(x, 0, 0, d_keys, beta, d_pos, d_loglik, d_subiter, d_theta, d_momentum);
+}
+// n_steps transitions in ONE launch: the tile's rows stay in registers, L^T is streamed again once per transition
+extern "C" int mfm_eslice_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, int32_t n_steps, int32_t thin,
+                              float* d_pos, double* d_loglik, int32_t* d_subiter_sum, int32_t* d_n_capped, float* d_traj_pos,
+                              double* d_traj_loglik, int32_t* d_subiter, double* d_theta, float* d_momentum, int32_t* d_subiter_max) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_loglik) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_loglik));
+  CHECKED(check_eslice(x, beta, true));
+  EsliceArgs e = eslice_args(x, 2, beta);
+  e.key_mode = key_mode; e.key = Key2{k0, k1}; e.keys = key_mode == 1 ? d_keys : nullptr; e.n_steps = n_steps; e.thin = thin;
+  e.pos = d_pos; e.loglik = d_loglik; e.subiter_sum = d_subiter_sum; e.n_capped = d_n_capped; e.traj_pos = d_traj_pos; e.traj_loglik = d_traj_loglik;
+  e.subiter = d_subiter; e.theta = d_theta; e.momentum = d_momentum; e.subiter_max = d_subiter_max;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_eslice(e, x->stream)) return too_large(x, "elliptical slice");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;
+  return MFM_OK;
+}
+extern "C" int mfm_eslice_launch_plan(int32_t dim, int32_t* h_tpw, int32_t* h_lds_bytes) {
+  if (!h_tpw || !h_lds_bytes) return fail(MFM_EINVAL, "mfm_eslice_launch_plan: null output pointer");
+  if (dim < 1) return fail(MFM_EINVAL, "mfm_eslice_launch_plan: dim must be positive (got %d)", dim);
+  int tpw; size_t sm;
+  eslice_plan((dim + 15) / 16 * 16, &tpw, &sm);
+  if (!tpw || sm > 160 * 1024) return fail(MFM_ETOOLARGE, "dim %d too large for the elliptical slice kernel", dim);
+  *h_tpw = tpw; *h_lds_bytes = (int32_t)sm;
   return MFM_OK;
 }
 

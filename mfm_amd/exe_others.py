@@ -1,7 +1,8 @@
 """Baseline runners -- drop-in for the reference's ``exe_others.py``, for the baselines that share the MFM hot path:
 adaptive tempered SMC on the MALA kernel (``exe_others.py:79-111``) and -- ``--do_svgd``, a build-side
 baseline the reference's script does not run -- Stein variational gradient descent on the same particles and target gradients
-(``bblackjax/vi/svgd.py``; ``mfm_svgd_step``).  The other baselines (flowMC, pocoMC, DDS, FAB: ``:44-76,114-296``) wrap third-party
+(``bblackjax/vi/svgd.py``; ``mfm_svgd_step``), parallel tempering (``--do_pt``) and, for the Cox process, elliptical slice
+sampling (``--do_eslice``; ``bblackjax/mcmc/elliptical_slice.py``, ``mfm_eslice_run``).  The other baselines (flowMC, pocoMC, DDS, FAB: ``:44-76,114-296``) wrap third-party
 samplers outside the scope and raise.
 
 ``run(dist, args, target_gn=None) -> (res[5], res_[5])`` as ``exe_others.py:22,376``: logpdf, Stein U / V, MMD, train time
@@ -27,6 +28,8 @@ logger = logging.getLogger(__name__)
 def run(dist, args, target_gn=None, return_extras=False):
     import torch
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s - %(message)s", datefmt="%m/%d/%Y %H:%M:%S", level=logging.INFO)
+    if getattr(args, "do_eslice", False):
+        return run_eslice(dist, args, target_gn, return_extras)
     if getattr(args, "do_pt", False):
         return run_pt(dist, args, target_gn, return_extras)
     if getattr(args, "do_svgd", False) and not getattr(args, "do_smc", False):
@@ -131,6 +134,75 @@ def run_svgd(dist, args, target_gn=None, return_extras=False):
     wandb.finish()
     if return_extras:
         return res, res_, dict(length_scales=length_scales, state=state, engine=eng, samples=particles)
+    eng.close()
+    return res, res_
+
+
+def check_eslice_args(args):
+    """``--do_eslice``'s argument checks, before any device work: the chain count."""
+    if getattr(args, "example", "pines") != "pines":
+        raise ValueError(f"--do_eslice needs --example pines (got {args.example}): elliptical slice sampling needs the Cox process's Gaussian prior factor")
+    if getattr(args, "do_smc", False) or getattr(args, "do_svgd", False) or getattr(args, "do_pt", False):
+        raise ValueError("--do_eslice runs alone: not with --do_smc, --do_svgd or --do_pt")
+    if int(args.num_chain) < 16 or int(args.num_chain) % 16:
+        raise ValueError(f"--do_eslice: num_chain ({args.num_chain}) must be a multiple of 16 (the kernel works on tiles of 16 chains)")
+    return int(args.num_chain)
+
+
+def run_eslice(dist, args, target_gn=None, return_extras=False):
+    """``--do_eslice``: elliptical slice sampling (``bblackjax/mcmc/elliptical_slice.py``) of the Cox process at beta = 1 from the
+    initial chains.  ``learning_iter`` transitions in one launch, timed as the train time, then ``eval_iter`` transitions with
+    ``thin=1`` whose draws give ``res[5]`` in ``--do_smc``'s shape.  Logged: the likelihood evaluations per transition, the capped
+    transitions, split R-hat and the multi-chain ESS per transition and per likelihood evaluation (the scale of a MALA step)."""
+    import torch
+    from . import diagnostics
+    from .bblackjax.mcmc import elliptical_slice as ES
+    n_chain = check_eslice_args(args)
+    learning_iter, n_iter = int(args.learning_iter), int(args.eval_iter)
+    key_target, key_sample, key_init, key_dist, key_fourier, key_gen = jr.split(jr.PRNGKey(args.seed), 6)     # :33
+    dist.initialize_model(key_dist, n_chain)                                                # :34
+    eng = Engine(dist, args, None, max_eval_samples=max(n_iter * n_chain, 16))
+    if eng.world > 1 or eng.n_valid != eng.n_local:
+        eng.close()
+        raise NotImplementedError("the elliptical slice baseline runs on one rank with num_chain a multiple of 16")
+    real_samples = None
+    if target_gn is not None:                                                               # :36-39
+        key_gen, key_loss = jr.split(key_target)
+        real_samples = torch.as_tensor(np.ascontiguousarray(dist.sample_rows(jr.split(key_gen, n_iter * n_chain)), dtype=np.float32), device=eng.dev)
+    logger.info(f"===== Starting training seed {args.seed} w/ {learning_iter} iterations =====")
+    logger.info(f"Elliptical slice sampling: {n_chain} chains")
+    algo = ES.elliptical_slice(dist.loglik)
+    state = algo.init(eng.local(dist.init_params))
+    k_train, k_eval = jr.split(key_sample)
+    train_start = time.time()
+    state, info = algo.step.run(k_train, state, learning_iter)
+    eng.ctx.sync()
+    train_time = time.time() - train_start
+    state, einfo = algo.step.run(k_eval, state, n_iter, thin=1)
+    mean_sub = float(einfo.mean_subiter.mean().item())
+    stats = {"eslice_mean_subiter": mean_sub, "eslice_max_subiter": int(max(info.max_subiter.max().item(), einfo.max_subiter.max().item())),
+             "eslice_capped": int(info.num_capped.sum().item() + einfo.num_capped.sum().item())}
+    logger.info(f"Likelihood evaluations per transition (mean over the evaluation run)= {mean_sub:.3f}; capped transitions= {stats['eslice_capped']}")
+    if n_iter >= 4:
+        cd = diagnostics.chain_diagnostics(einfo.positions, ctx=eng.ctx)
+        rhat, multi = cd.rhat.double(), cd.ess.double() / (float(n_chain) * n_iter)
+        stats.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item())
+        for scale, div in (("step", 1.0), ("eval", mean_sub)):
+            stats.update({f"ess_multichain_per_{scale}_min": multi.min().item() / div, f"ess_multichain_per_{scale}_median": multi.median().item() / div,
+                          f"ess_multichain_per_{scale}_mean": multi.mean().item() / div})
+        logger.info(f"Split R-hat (max, median over coordinates)= {stats['rhat_max']:.4g}, {stats['rhat_median']:.4g}")
+        logger.info("Multi-chain ESS per transition and chain (min, median, mean over coordinates)= "
+                    + ", ".join(f"{stats['ess_multichain_per_step_' + k]:.4g}" for k in ("min", "median", "mean")))
+    flow_samples = einfo.positions.reshape(-1, einfo.positions.shape[-1]).contiguous()       # ("not really flow but MCMC")
+    logpdf = _logprob_any(eng, flow_samples).mean().item()
+    stein = stein_disc(eng, flow_samples)
+    mmd = eng.ctx.max_mean_disc(real_samples, flow_samples) if real_samples is not None else 0.0
+    wandb.log({"train_time": train_time, "logpdf": logpdf, "KSD U-stat": stein[0], "KSD V-stat": stein[1], **stats})
+    res = np.array([logpdf, stein[0], stein[1], mmd, train_time])
+    res_ = res.copy()                                                                       # same particles, as the SMC baseline (:108-109)
+    wandb.finish()
+    if return_extras:
+        return res, res_, dict(state=state, engine=eng, samples=flow_samples, stats=stats, info=info, eval_info=einfo)
     eng.close()
     return res, res_
 

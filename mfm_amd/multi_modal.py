@@ -6,7 +6,7 @@ values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=25
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
 ``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic; ``--hmc_adapt chees``: the N steps are ChEES-HMC iterations, which adapt the step size and the trajectory length across the chains, and the HMC steps then make a jittered number of leapfrog steps in place of ``--hmc_steps``),
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
-``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); the other baselines
+``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); ``--do_eslice`` (``--example pines``) runs elliptical slice sampling on the Cox process (``bblackjax/mcmc/elliptical_slice.py``, one rank); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
 
 Multi-GPU: launch with ``python -m torch.distributed.run --nproc-per-node N -m mfm_amd.multi_modal ...``; chains are
@@ -76,7 +76,11 @@ def main(args):
 
     N_PARAM = args.dim
     job_type = "mcmc_per_flow_steps=" + str(args.mcmc_per_flow_steps) + ",learning_iter=" + str(args.learning_iter) + (",hutchs" if args.hutchs else "")
-    if getattr(args, "do_pt", False):
+    if getattr(args, "do_eslice", False):
+        from .exe_others import check_eslice_args
+        check_eslice_args(args)                                                         # (before any device work)
+        job_type = "Elliptical slice sampling"
+    elif getattr(args, "do_pt", False):
         from .exe_others import check_pt_args
         check_pt_args(args)                                                             # (before any device work)
         job_type = "Parallel tempering"
@@ -89,7 +93,7 @@ def main(args):
     for seed in seeds:
         args.seed = seed
         wandb.init(project=args.example, config=args, group="dim=" + str(N_PARAM), job_type=job_type)
-        if args.do_smc or args.do_svgd or getattr(args, "do_pt", False):
+        if args.do_smc or args.do_svgd or getattr(args, "do_pt", False) or getattr(args, "do_eslice", False):
             _res, _res_ = run_others(dist, args, dist.sample_model)                     # :126-127
         else:
             _res, _res_ = run(dist, args, dist.sample_model, log_every=args.log_every)  # :129
@@ -203,6 +207,10 @@ def build_parser():
     parser.add_argument('--pt_temps', type=int, default=8)
     parser.add_argument('--pt_beta_min', type=float, default=0.01)
     parser.add_argument('--pt_local_steps', type=int, default=4)
+    # the elliptical slice baseline (exe_others.run_eslice; --example pines only): --learning_iter transitions of every chain at beta = 1 in one
+    # launch, then --eval_iter kept ones; no step size and no gradient (mfm_amd/bblackjax/mcmc/elliptical_slice.py)
+    parser.add_argument('--do_eslice', dest='do_eslice', action='store_true')
+    parser.set_defaults(do_eslice=False)
     return parser
 
 
