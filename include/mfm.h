@@ -404,6 +404,42 @@ int mfm_eslice_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, con
                    int32_t* d_subiter, double* d_theta, float* d_momentum /* the LAST transition's info, as mfm_eslice_step's */,
                    int32_t* d_subiter_max);
 int mfm_eslice_launch_plan(int32_t dim, int32_t* h_tpw, int32_t* h_lds_bytes);
+/* HAMILTONIAN MONTE CARLO FOR THE COX PROCESS on the 16-chain K^-1 GEMM tile (lgcp_hmc.hip), the target that mfm_hmc_* refuses.  The
+ * four calls mirror mfm_hmc_step / _step_keys / _run / _warmup argument for argument: the same keys and key schedules, the same in-place
+ * state -- the MALA state, made by mfm_mala_init on this context -- the same outputs, and the same dual-averaging recursion in the warmup.
+ * One step of chain b with chain key kb: k_mom = split(kb, 2)[0], k_acc = split(kb, 2)[1]; momentum p_j = normal(k_mom, (dim,))[j] in
+ * float64; H0 = -logp + sum(p^2) / 2; num_steps velocity-Verlet steps, each p += eps/2 g; x = (float)(x + eps p); y = K^-1 (x - mu)
+ * by ONE tile GEMM; g = beta (c - a exp(x)) - y; p += eps/2 g; the log-density of the end point from the last step's float64 row sums;
+ * accepted when uniform(k_acc) < min(1, exp(H0 - H_end)) (NaN rejects).  oracle/hmc.py on targets.Tempered(dist, beta) restates it.
+ * One workgroup per 16 chains; x, p and g of a tile stay in registers over the trajectory, and mfm_cox_hmc_run / _warmup make all
+ * their steps in ONE launch (an accepted row stores its end point, every step reads its start from the state arrays): bit-identical with
+ * n_steps single-step calls on the run's keys; step m of a warmup has the bits of mfm_cox_hmc_step_keys with the scalar step size
+ * d_step_traj[m][b].  Rows of a tile adapt different step sizes at the same num_steps.
+ * Checks: those of the mfm_hmc_* call of the same name, in its order; then a target other than the Cox process: MFM_EUNSUPPORTED (use
+ * mfm_hmc_*); an installed inverse mass: MFM_EUNSUPPORTED (the kernel runs at unit mass); n_chain_local not a multiple of 16:
+ * MFM_EINVAL; dim beyond the instances (dim > 1024, a 32 x 32 grid): MFM_ETOOLARGE.  A rejected call touches nothing; the calls only
+ * enqueue.  A sharded context (n_chain_total, chain_offset) is served: the chains are independent.
+ * mfm_cox_hmc_launch_plan (host only, no context): *h_tpw, the column tiles per wave of the kernel instance that serves dim (1, 2, 4 or
+ * 8), and *h_lds_bytes, the dynamic LDS of one workgroup. */
+int mfm_cox_hmc_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, double step_size, int32_t num_steps,
+                     float* d_pos, double* d_logp, float* d_grad, float* d_acceptance_rate, uint8_t* d_is_accepted);
+int mfm_cox_hmc_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double step_size, int32_t num_steps,
+                          float* d_pos, double* d_logp, float* d_grad, float* d_acceptance_rate, uint8_t* d_is_accepted);
+int mfm_cox_hmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                    double beta, double step_size, int32_t num_steps /* leapfrog steps per HMC step */,
+                    int32_t n_steps, int32_t thin,
+                    float* d_pos, double* d_logp, float* d_grad,
+                    int32_t* d_n_accepted, double* d_acc_sum,
+                    float* d_acceptance_rate, uint8_t* d_is_accepted,
+                    float* d_traj_pos, double* d_traj_logp);
+int mfm_cox_hmc_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                       double beta, double step0, int32_t num_steps /* leapfrog steps per HMC step */,
+                       int32_t n_steps, double target_accept,
+                       float* d_pos, double* d_logp, float* d_grad,
+                       double* d_step_avg, double* d_step_last,
+                       int32_t* d_n_accepted, double* d_acc_sum,
+                       double* d_step_traj);
+int mfm_cox_hmc_launch_plan(int32_t dim, int32_t* h_tpw, int32_t* h_lds_bytes);
 /* STEP-SIZE WARMUP OF THE NO-U-TURN SAMPLER: n_steps NUTS transitions in ONE launch, as mfm_nuts_run (chain resident in registers,
  * key_mode 0 / 1 and their key schedules, max_tree_depth / divergence_threshold and the installed inverse mass as there), in which every
  * chain adapts its OWN step size by the dual averaging of mfm_hmc_warmup -- the same recursion, constants and clamp, eps_1 = step0

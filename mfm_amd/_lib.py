@@ -80,6 +80,11 @@ _SIGS = {
     "mfm_eslice_step_keys": (C.c_int, [_P, _P, C.c_double, _P, _P, _P, _P, _P]),
     "mfm_eslice_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_eslice_launch_plan": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mfm_cox_hmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P]),
+    "mfm_cox_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
+    "mfm_cox_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_cox_hmc_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_cox_hmc_launch_plan": (C.c_int, [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mfm_nuts_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_nuts_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_double, C.c_int32, C.c_int32, _P, _P, _P,
@@ -221,6 +226,14 @@ def eslice_launch_plan(dim):
     elliptical slice kernel at ``dim``."""
     tpw, sm = C.c_int32(), C.c_int32()
     _chk(load().mfm_eslice_launch_plan(int(dim), C.byref(tpw), C.byref(sm)))
+    return tpw.value, sm.value
+
+
+def cox_hmc_launch_plan(dim):
+    """``mfm_cox_hmc_launch_plan`` (host only): ``(column tiles per wave of the kernel instance, LDS bytes per workgroup)`` of the
+    Cox process's HMC kernel at ``dim``."""
+    tpw, sm = C.c_int32(), C.c_int32()
+    _chk(load().mfm_cox_hmc_launch_plan(int(dim), C.byref(tpw), C.byref(sm)))
     return tpw.value, sm.value
 
 
@@ -547,6 +560,41 @@ class Context:
         _chk(self.lib.mfm_hmc_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
                                      int(num_steps), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                      _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
+
+    # HMC for the Cox process on the 16-chain GEMM tile (lgcp_hmc.hip): the keyword names of the hmc_* siblings; the state is the MALA
+    # state (mala_init)
+    def cox_hmc_step(self, key, beta, step_size, num_steps, pos, logp, grad, acc=None, is_acc=None):
+        """``mfm_cox_hmc_step``: one HMC step of every local chain of a Cox process context, state updated in place."""
+        _chk(self.lib.mfm_cox_hmc_step(self.h, int(key[0]), int(key[1]), float(beta), float(step_size), int(num_steps),
+                                       _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(acc, F32), _ptr(is_acc, U8)))
+
+    def cox_hmc_step_keys(self, keys, beta, step_size, num_steps, pos, logp, grad, acc=None, is_acc=None):
+        """``mfm_cox_hmc_step_keys``: ``keys`` is an int32/uint32 device tensor [n_chain_local, 2], one key per chain."""
+        _chk(self.lib.mfm_cox_hmc_step_keys(self.h, _ptr(keys, I32), float(beta), float(step_size), int(num_steps),
+                                            _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(acc, F32), _ptr(is_acc, U8)))
+
+    def cox_hmc_run(self, key, beta, step_size, num_steps, n_steps, pos, logp, grad, thin=0, n_acc=None, acc_sum=None, acc=None,
+                    is_acc=None, traj_pos=None, traj_logp=None, key_mode=None):
+        """``mfm_cox_hmc_run``: ``n_steps`` HMC steps of ``num_steps`` leapfrog steps each in one launch; arguments as ``hmc_run``'s."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_cox_hmc_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size),
+                                      int(num_steps), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                      _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
+                                      _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    def cox_hmc_warmup(self, key, beta, step0, num_steps, n_steps, target_accept, pos, logp, grad, step_avg, step_last=None, n_acc=None,
+                       acc_sum=None, step_traj=None, key_mode=None):
+        """``mfm_cox_hmc_warmup``: the run with every chain adapting its own step size by dual averaging; arguments and outputs as
+        ``hmc_warmup``'s."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        self._warmup_sizes(n_steps, step_avg, step_last, n_acc, acc_sum, step_traj)
+        _chk(self.lib.mfm_cox_hmc_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0),
+                                         int(num_steps), int(n_steps), float(target_accept), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                         _ptr(step_avg, F64), _ptr(step_last, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(step_traj, F64)))
 
     _inv_mass = None      # host copy of the installed vector (None: unit mass), what set_inverse_mass compares with
 

@@ -14,7 +14,12 @@ kernel carries ``kernel.run(rng_key, state, logdensity_fn, step_size, num_integr
 steps in ONE launch (``mfm_hmc_run``) with the chain resident on the device between steps, and ``kernel.warmup(rng_key, state,
 logdensity_fn, step_size, num_integration_steps, num_steps, target_acceptance_rate=0.8, keep_step_sizes=False)``: ``num_steps`` HMC
 steps in one launch (``mfm_hmc_warmup``) in which every chain adapts its own step size from ``step_size`` by dual averaging towards
-the target acceptance probability (Hoffman & Gelman's constants; the recursion: ``include/mfm.h``)."""
+the target acceptance probability (Hoffman & Gelman's constants; the recursion: ``include/mfm.h``).
+
+The kernel dispatches by target: the log-Gaussian Cox process (``--example pines``), whose gradient needs the ``K^-1`` GEMM tile, goes
+to ``mfm_cox_hmc_step`` / ``_step_keys`` / ``_run`` / ``_warmup`` (``lgcp_hmc.hip``) with the same states and infos; every other
+target goes to ``mfm_hmc_*``.  The Cox kernel runs at unit mass and at one leapfrog count: ``inverse_mass_matrix`` or
+``num_integration_steps_per_step`` with a Cox target is a ``ValueError`` before any device work."""
 from typing import Callable, NamedTuple
 
 import numpy as np
@@ -129,20 +134,38 @@ def _mass_engine(dist, inverse_mass_matrix):
     return eng
 
 
+def _is_cox(dist):
+    return getattr(dist, "kind", None) == "lgcp"
+
+
+def _cox_engine(dist, inverse_mass_matrix, num_integration_steps_per_step=None):
+    """The engine of a Cox process target for the ``cox_hmc_*`` calls; ``ValueError`` (before any device work) for what its kernel
+    does not serve.  Unit mass is installed: the context may carry a vector from another call."""
+    if inverse_mass_matrix is not None:
+        raise ValueError("inverse_mass_matrix is not served on the Cox process: its HMC kernel (mfm_cox_hmc_*) runs at unit mass")
+    if num_integration_steps_per_step is not None:
+        raise ValueError("num_integration_steps_per_step is not served on the Cox process: mfm_hmc_run_lengths / ChEES have no Cox kernel")
+    eng = _engine(dist)
+    eng.ctx.set_inverse_mass(None)
+    return eng
+
+
 def build_kernel():
     def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, inverse_mass_matrix=None):
         """One key: chain b draws from ``split(rng_key, n_chain_total)[chain_offset + b]``; keys ``[n_chain_local, 2]``: the caller's
         own vmap, chain b draws from ``rng_key[b]``."""
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _mass_engine(dist, inverse_mass_matrix)
+        cox = _is_cox(dist)
+        eng = _cox_engine(dist, inverse_mass_matrix) if cox else _mass_engine(dist, inverse_mass_matrix)
+        step, step_keys = (eng.ctx.cox_hmc_step, eng.ctx.cox_hmc_step_keys) if cox else (eng.ctx.hmc_step, eng.ctx.hmc_step_keys)
         t = eng.torch
         pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()      # states are values
         acc = t.empty(pos.shape[0], device=pos.device, dtype=t.float32)
         isacc = t.empty(pos.shape[0], device=pos.device, dtype=t.uint8)
         if getattr(rng_key, "ndim", 1) == 2:
-            eng.ctx.hmc_step_keys(_device_keys(t, rng_key, pos.device), beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
+            step_keys(_device_keys(t, rng_key, pos.device), beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
         else:
-            eng.ctx.hmc_step(rng_key, beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
+            step(rng_key, beta, step_size, num_integration_steps, pos, logp, grad, acc, isacc)
         return HMCState(pos, logp, grad), HMCInfo(acc, isacc.bool())
 
     def run(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int, thin: int = 0,
@@ -152,9 +175,13 @@ def build_kernel():
         Bit-identical with that loop.  ``thin >= 1`` keeps the state after every ``thin``-th step.
         ``num_integration_steps_per_step`` (array-like of ``num_steps`` ints, or a callable ``i -> int``) gives step j its own number of
         leapfrog steps in place of ``num_integration_steps`` (``mfm_hmc_run_lengths``: the sampler ``chees_adaptation`` adapts)."""
-        lengths = None if num_integration_steps_per_step is None else integration_step_counts(num_integration_steps_per_step, num_steps)
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _mass_engine(dist, inverse_mass_matrix)
+        cox = _is_cox(dist)
+        if cox:
+            eng = _cox_engine(dist, inverse_mass_matrix, num_integration_steps_per_step)
+        lengths = None if num_integration_steps_per_step is None else integration_step_counts(num_integration_steps_per_step, num_steps)
+        if not cox:
+            eng = _mass_engine(dist, inverse_mass_matrix)
         t = eng.torch
         num_steps, thin = int(num_steps), int(thin)
         pos, logp, grad = state.position.clone(), state.logdensity.clone(), state.logdensity_grad.clone()
@@ -174,8 +201,8 @@ def build_kernel():
             eng.ctx.hmc_run_lengths(rng_key, beta, step_size, t.as_tensor(lengths, device=dev), pos, logp, grad, thin=thin, n_acc=n_acc,
                                     acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp, total_leapfrog=total)
             return HMCState(pos, logp, grad), HMCRunLengthsInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp, int(total.item()))
-        eng.ctx.hmc_run(rng_key, beta, step_size, num_integration_steps, num_steps, pos, logp, grad, thin=thin, n_acc=n_acc,
-                        acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp)
+        (eng.ctx.cox_hmc_run if cox else eng.ctx.hmc_run)(rng_key, beta, step_size, num_integration_steps, num_steps, pos, logp, grad, thin=thin,
+                                                          n_acc=n_acc, acc_sum=acc_sum, acc=acc, is_acc=isacc, traj_pos=traj_pos, traj_logp=traj_logp)
         return HMCState(pos, logp, grad), HMCRunInfo(acc_sum / num_steps, n_acc, HMCInfo(acc, isacc.bool()), traj_pos, traj_logp)
 
     def warmup(rng_key, state: HMCState, logdensity_fn: Callable, step_size: float, num_integration_steps: int, num_steps: int,
@@ -184,9 +211,11 @@ def build_kernel():
         ``target_acceptance_rate``; keys as ``run``'s (one key: step-major; ``[n_chain_local, 2]``: chain-major).  Returns the state
         after the steps and an ``HMCWarmupInfo``; ``info.pooled_step_size`` is the value to sample with."""
         dist, beta = resolve_logdensity(logdensity_fn)
-        eng = _mass_engine(dist, inverse_mass_matrix)
-        return _warmup(lambda key, pos, logp, grad, **out: eng.ctx.hmc_warmup(key, beta, step_size, num_integration_steps, int(num_steps),
-                                                                              target_acceptance_rate, pos, logp, grad, **out),
+        cox = _is_cox(dist)
+        eng = _cox_engine(dist, inverse_mass_matrix) if cox else _mass_engine(dist, inverse_mass_matrix)
+        call = eng.ctx.cox_hmc_warmup if cox else eng.ctx.hmc_warmup
+        return _warmup(lambda key, pos, logp, grad, **out: call(key, beta, step_size, num_integration_steps, int(num_steps),
+                                                                target_acceptance_rate, pos, logp, grad, **out),
                        eng, rng_key, state, num_steps, keep_step_sizes)
 
     kernel.run = run
@@ -200,7 +229,10 @@ class hmc:
 
     def __new__(cls, logdensity_fn: Callable, step_size: float, num_integration_steps: int, inverse_mass_matrix=None) -> SamplingAlgorithm:
         kernel = cls.build_kernel()
-        minv = check_inverse_mass(inverse_mass_matrix, getattr(resolve_logdensity(logdensity_fn)[0], "dim", None))
+        dist = resolve_logdensity(logdensity_fn)[0]
+        if _is_cox(dist) and inverse_mass_matrix is not None:
+            raise ValueError("inverse_mass_matrix is not served on the Cox process: its HMC kernel (mfm_cox_hmc_*) runs at unit mass")
+        minv = check_inverse_mass(inverse_mass_matrix, getattr(dist, "dim", None))
 
         def init_fn(position):
             return cls.init(position, logdensity_fn)

@@ -22,6 +22,7 @@
 #include "chees.hip"
 #include "pt.hip"
 #include "eslice.hip"
+#include "lgcp_hmc.hip"
 #include "fm.hip"
 #include "optim.hip"
 #include "wgrad_sk.hip"
@@ -1235,6 +1236,90 @@ extern "C" int mfm_mala_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k
   // state in and out once, as mfm_mala_run; the step sizes that were kept
   x->ctr[CTR_MALA] += (int64_t)B * n_steps;
   x->ctr[CTR_MALA_BYTES] += (int64_t)B * 4 * (4 * d + 4) + (int64_t)B * 8 * (1 + (d_step_last ? 1 : 0) + (d_step_traj ? n_steps : 0));
+  return MFM_OK;
+}
+
+// ---- HMC for the Cox process on the 16-chain GEMM tile (lgcp_hmc.hip) ----
+// The entry points mirror mfm_hmc_step / _step_keys / _run / _warmup argument for argument and make their checks in their order; then
+// the refusals of their own below.  A rejected call touches nothing.
+static int check_cox_hmc(mfm_ctx* x) {
+  if (x->net.T.kind != MFM_TARGET_LGCP)
+    return fail(MFM_EUNSUPPORTED, "mfm_cox_hmc_* serves the Cox process on the K^-1 GEMM tile: use mfm_hmc_* (mfm_hmc_step, mfm_hmc_run, mfm_hmc_warmup) for this target");
+  if (!x->h_inv_mass.empty())
+    return fail(MFM_EUNSUPPORTED, "the Cox process's HMC runs at unit mass: remove the installed inverse mass (mfm_hmc_set_inverse_mass with n = 0)");
+  if (x->cfg.n_chain_local % 16) return fail(MFM_EINVAL, "n_chain_local (%d) must be a multiple of 16 (one tile of 16 chains per workgroup)", x->cfg.n_chain_local);
+  int tpw; size_t sm;
+  cox_hmc_plan(x->net.dp, &tpw, &sm);
+  if (!tpw || sm > 160 * 1024) return too_large(x, "Cox process HMC");
+  return MFM_OK;
+}
+static CoxHmcArgs cox_hmc_args(mfm_ctx* x, int run, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps,
+                               float* d_pos, double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
+  CoxHmcArgs a; memset(&a, 0, sizeof a);
+  a.T = x->net.T; a.dp = x->net.dp; a.run = run; a.key = Key2{k0, k1}; a.keys = d_keys;
+  a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local; a.num_steps = num_steps;
+  a.beta = beta; a.eps = step;
+  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.acc_prob = d_acc; a.accepted = d_isacc;
+  a.t = RunTail{0, 1, 0, nullptr, nullptr, nullptr, nullptr};
+  return a;
+}
+static int cox_hmc_launch(mfm_ctx* x, const CoxHmcArgs& a, bool warm) {
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_cox_hmc(a, warm, x->stream)) return too_large(x, "Cox process HMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * a.t.n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+static int cox_hmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos,
+                               double* d_logp, float* d_grad, float* d_acc, uint8_t* d_isacc) {
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_num_steps(num_steps));
+  CHECKED(check_cox_hmc(x));
+  return cox_hmc_launch(x, cox_hmc_args(x, 0, k0, k1, d_keys, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc), false);
+}
+extern "C" int mfm_cox_hmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, int num_steps, float* d_pos, double* d_logp,
+                                float* d_grad, float* d_acc, uint8_t* d_isacc) { use_ctx(x);
+  return cox_hmc_step_common(x, k0, k1, nullptr, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+}
+extern "C" int mfm_cox_hmc_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, double step, int num_steps, float* d_pos, double* d_logp,
+                                     float* d_grad, float* d_acc, uint8_t* d_isacc) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return cox_hmc_step_common(x, 0, 0, d_keys, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+}
+// n_steps HMC steps in ONE launch: the tile's x, p and g stay in registers, K^-1 is streamed again once per leapfrog step
+extern "C" int mfm_cox_hmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, int32_t num_steps,
+                               int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, int32_t* d_n_acc, double* d_acc_sum,
+                               float* d_acc, uint8_t* d_isacc, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  CHECKED(check_state(d_pos, d_logp, d_grad, step));
+  CHECKED(check_num_steps(num_steps));
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  CHECKED(check_cox_hmc(x));
+  CoxHmcArgs a = cox_hmc_args(x, 1, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, num_steps, d_pos, d_logp, d_grad, d_acc, d_isacc);
+  a.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
+  return cox_hmc_launch(x, a, false);
+}
+// the run with a per-row step size, adapted by dual averaging on the row's owner lanes (mfm_hmc_warmup's recursion and outputs)
+extern "C" int mfm_cox_hmc_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, int32_t num_steps,
+                                  int32_t n_steps, double target_accept, float* d_pos, double* d_logp, float* d_grad, double* d_step_avg,
+                                  double* d_step_last, int32_t* d_n_acc, double* d_acc_sum, double* d_step_traj) { use_ctx(x);
+  CHECKED(warmup_check(x, key_mode, d_keys, step0, n_steps, target_accept, d_pos, d_logp, d_grad, d_step_avg));
+  CHECKED(check_num_steps(num_steps));
+  CHECKED(check_cox_hmc(x));
+  CoxHmcArgs a = cox_hmc_args(x, 1, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, num_steps, d_pos, d_logp, d_grad, nullptr, nullptr);
+  a.t = RunTail{key_mode, n_steps, 0, d_n_acc, d_acc_sum, nullptr, nullptr};      // (a warmup keeps no trajectory)
+  a.w = WarmupArgs{target_accept, d_step_avg, d_step_last, d_step_traj, nullptr, nullptr};
+  return cox_hmc_launch(x, a, true);
+}
+extern "C" int mfm_cox_hmc_launch_plan(int32_t dim, int32_t* h_tpw, int32_t* h_lds_bytes) {
+  if (!h_tpw || !h_lds_bytes) return fail(MFM_EINVAL, "mfm_cox_hmc_launch_plan: null output pointer");
+  if (dim < 1) return fail(MFM_EINVAL, "mfm_cox_hmc_launch_plan: dim must be positive (got %d)", dim);
+  int tpw; size_t sm;
+  cox_hmc_plan((dim + 15) / 16 * 16, &tpw, &sm);
+  if (!tpw || sm > 160 * 1024) return fail(MFM_ETOOLARGE, "dim %d too large for the Cox process HMC kernel", dim);
+  *h_tpw = tpw; *h_lds_bytes = (int32_t)sm;
   return MFM_OK;
 }
 

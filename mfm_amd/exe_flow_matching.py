@@ -222,6 +222,7 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
 
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
     use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
+    hmc_step = eng.ctx.cox_hmc_step if getattr(dist, "kind", None) == "lgcp" else eng.ctx.hmc_step      # (by target, as bblackjax.mcmc.hmc)
     if use_nuts:
         info["nuts_acc"] = t.empty(n, device=eng.dev, dtype=t.float64)
 
@@ -238,8 +239,8 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
             conditional_importance_sampling(rng_key, beta, pos, logp)
         elif do_flow:
             eng.ctx.flow_step(mode, rng_key, beta, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["nsteps"])
-        elif use_hmc:          # build-side mode (--mcmc_kernel hmc): the iteration's MCMC move is an HMC step (mfm_hmc_step) instead of :313
-            eng.ctx.hmc_step(rng_key, beta, args.step_size, hmc_num_steps(args, count), pos, logp, grad, info["acc"], info["isacc"])
+        elif use_hmc:          # build-side mode (--mcmc_kernel hmc): the iteration's MCMC move is an HMC step (mfm_hmc_step; the Cox process: mfm_cox_hmc_step) instead of :313
+            hmc_step(rng_key, beta, args.step_size, hmc_num_steps(args, count), pos, logp, grad, info["acc"], info["isacc"])
         elif use_nuts:         # build-side mode (--mcmc_kernel nuts): a No-U-turn transition (mfm_nuts_step); it always takes its tree's proposal
             eng.ctx.nuts_step(rng_key, beta, args.step_size, int(getattr(args, "max_tree_depth", 10)), pos, logp, grad, acceptance_rate=info["nuts_acc"])
             info["acc"].copy_(info["nuts_acc"]); info["isacc"].fill_(1)
@@ -323,6 +324,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     if use_real_samples and target_gn is None:
         raise ValueError("mcmc_per_flow_steps < 0 trains on exact samples and needs a target with sample_model (:382-386)")
     check_adapt_args(args)                                                                  # --adapt_steps (build-side addition)
+    check_cox_args(dist, args)                                                              # --example pines: what its HMC kernel does not serve
     learning_iter = args.learning_iter
     iter_per_temp = args.anneal_iter // args.num_anneal_temp                                # :330
     n_iter, n_chain = args.eval_iter, args.num_chain
@@ -513,6 +515,25 @@ def check_adapt_args(args):
     if nuts_adapt == "tree" and getattr(args, "mcmc_kernel", "mala") != "nuts":
         raise ValueError("--nuts_adapt tree adapts on the No-U-turn sampler's own trees: it needs --mcmc_kernel nuts")
     return n_steps
+
+
+def check_cox_args(dist, args):
+    """``--example pines``: the gradient samplers reach the Cox process through ``mfm_cox_hmc_*`` alone (``--mcmc_kernel hmc``, its
+    ``--adapt_steps`` dual-averaging warmup, ``--ess_steps``); what has no Cox kernel is named here, before any device work."""
+    if getattr(dist, "kind", None) != "lgcp" or any(getattr(args, f, False) for f in ("do_eslice", "do_smc", "do_svgd")):
+        return                                      # (those baselines do not read --mcmc_kernel or the adaptation flags)
+    kern = getattr(args, "mcmc_kernel", "mala")
+    if getattr(args, "do_pt", False):
+        raise ValueError("--do_pt is not served with --example pines: parallel tempering (mfm_pt_run) has no local move for the Cox process")
+    if kern == "nuts":
+        raise ValueError("--mcmc_kernel nuts is not served with --example pines: the No-U-turn sampler has no Cox process kernel (use --mcmc_kernel hmc)")
+    if getattr(args, "adapt_mass", False):
+        raise ValueError("--adapt_mass is not served with --example pines: the Cox process's HMC kernel (mfm_cox_hmc_*) runs at unit mass")
+    if getattr(args, "hmc_adapt", "dual") == "chees":
+        raise ValueError("--hmc_adapt chees is not served with --example pines: ChEES (mfm_chees_warmup, mfm_hmc_run_lengths) has no Cox process kernel "
+                         "(use the default --hmc_adapt dual)")
+    if kern == "hmc" and int(getattr(dist, "dim", 0)) > 1024:
+        raise ValueError(f"--mcmc_kernel hmc with --example pines serves dim <= 1024, a 32 x 32 grid (got {dist.dim}): give --force_dim")
 
 
 def hmc_num_steps(args, i):

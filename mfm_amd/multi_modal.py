@@ -5,6 +5,7 @@ Additions (defaults leave the reference behaviour untouched): ``--force_dim`` / 
 values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=256 / 4096-chain configuration;
 ``multi_modal.py:52,55`` fix 64 / 1024), ``--log_every`` sets how often metrics are copied to the host, ``--ess_steps N`` measures the effective sample size per step of the run's ``--mcmc_kernel`` after training (for ``hmc`` and ``nuts`` also per gradient evaluation; ``--mcmc_kernel nuts --max_tree_depth D`` is the No-U-turn sampler),
 ``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic; ``--hmc_adapt chees``: the N steps are ChEES-HMC iterations, which adapt the step size and the trajectory length across the chains, and the HMC steps then make a jittered number of leapfrog steps in place of ``--hmc_steps``),
+with ``--example pines`` ``--mcmc_kernel hmc``, the ``--hmc_adapt dual`` warmup and ``--ess_steps`` run on the Cox process's own HMC kernel (``mfm_cox_hmc_*``, dim <= 1024: ``--force_dim``); ``--adapt_mass``, ``--hmc_adapt chees``, ``--mcmc_kernel nuts`` and ``--do_pt`` are refused there,
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); ``--do_eslice`` (``--example pines``) runs elliptical slice sampling on the Cox process (``bblackjax/mcmc/elliptical_slice.py``, one rank); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -20,7 +21,7 @@ import numpy as np
 from . import random as jr
 from . import wandb_shim as wandb
 from .distributions import GaussianMixture, LogGaussianCoxPines, PhiFour
-from .exe_flow_matching import run
+from .exe_flow_matching import check_cox_args, run
 from .exe_others import run as run_others
 
 
@@ -88,6 +89,7 @@ def main(args):
         job_type = "Adaptive tempered SMC"                                              # :110-111
     elif args.do_svgd:
         job_type = "SVGD"
+    check_cox_args(dist, args)                                                          # (--example pines: before any device work, after the baselines' own checks)
     seeds = [args.seed] if args.seed else [i ** 10 for i in range(10)]                  # :118
     res, res_ = [], []
     for seed in seeds:
