@@ -290,6 +290,32 @@ int mfm_hmc_run_lengths(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1
                         float* d_acceptance_rate, uint8_t* d_is_accepted,
                         float* d_traj_pos, double* d_traj_logp,
                         int64_t* d_total_leapfrog);
+/* MICROCANONICAL LANGEVIN MONTE CARLO (MCLMC: Robnik, De Luca, Silverstein & Seljak 2023; Robnik & Seljak 2024; blackjax.mclmc) -- a
+ * BUILD-SIDE MODE like mfm_hmc_*; tests/mclmc_ref.py restates it in float64 and is the definition.  A chain is (d_pos, d_logp, d_grad)
+ * as mfm_mala_init leaves them plus a UNIT momentum d_momentum, double[n_chain_local][dim].  One step of size step_size is the
+ * palindromic schedule B(b_0 eps) { A(a_k eps), value and gradient, B(b_k eps) }_k (integrator 0: leapfrog, one gradient; 1: McLachlan's
+ * minimal-norm scheme, two) of the exact momentum flow B and the drift A, then the partial refresh u <- (u + nu z) / |u + nu z| with
+ * nu = sqrt((exp(2 step_size / L) - 1) / dim) and z from split(chain key, 2)[0]; L = +inf gives nu = 0 and draws nothing.  There is NO
+ * accept test: every step is taken; its energy change dE = sum dK - (logp_end - logp_start) is reported and the chain is not repaired
+ * when it is not finite.  The calls only enqueue; shards (n_chain_total != n_chain_local) are served.
+ * Checks, in this order, a rejected call touching nothing: state pointers (and keys / key_mode / n_steps / thin as mfm_hmc_run);
+ * MFM_EUNSUPPORTED for the Cox process (mfm_hmc_step's message) and for an installed inverse mass (unit metric only); MFM_EINVAL naming
+ * the argument for dim < 2, step_size not positive, L not positive or NaN, L so small that nu overflows, integrator outside {0, 1}.
+ * mfm_mclmc_init: u_b = z / |z|, z_j = normal64(split(key, n_chain_total)[chain_offset + b], j, dim). */
+int mfm_mclmc_init(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double* d_momentum);
+/* one step; chain b uses split(key, n_chain_total)[chain_offset + b] (or d_keys[b]).  d_energy_change / d_kinetic_change: double[B], may be null */
+int mfm_mclmc_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, double step_size, double L, int integrator,
+                   float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_energy_change, double* d_kinetic_change);
+int mfm_mclmc_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double step_size, double L, int integrator,
+                        float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_energy_change, double* d_kinetic_change);
+/* n_steps steps in ONE launch, bit-identical with n_steps single-step calls; key_mode, the step keys, thin and the trajectory layout are
+ * mfm_hmc_run's.  Optional outputs (NULL to skip): d_de_sum / d_de_sumsq double[B], the sums of dE and dE^2 over the steps in step
+ * order; d_n_nonfinite int32[B], the steps whose dE is not finite; d_energy_trace double[n_steps][B], every step's dE. */
+int mfm_mclmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                  double beta, double step_size, double L, int integrator, int32_t n_steps, int32_t thin,
+                  float* d_pos, double* d_logp, float* d_grad, double* d_momentum,
+                  double* d_de_sum, double* d_de_sumsq, int32_t* d_n_nonfinite, double* d_energy_trace,
+                  float* d_traj_pos, double* d_traj_logp);
 /* ChEES-HMC WARMUP (Hoffman, Radul & Sountsov 2021; blackjax's chees_adaptation): n_iter HMC steps of ALL chains in which the step size
  * and the trajectory length are adapted ACROSS the chains; tests/chees_ref.py restates it in float64 and is the definition.  The call
  * only enqueues (four launches per iteration, chees.hip); eps_t, T_t, L_t and the optimizer's state live in device memory.

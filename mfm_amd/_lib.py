@@ -69,6 +69,11 @@ _SIGS = {
     "mfm_hmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
     "mfm_hmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mfm_hmc_run_lengths": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_mclmc_init": (C.c_int, [_P, _U32, _U32, _P]),
+    "mfm_mclmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "mfm_mclmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "mfm_mclmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
+                                _P, _P, _P, _P]),
     "mfm_chees_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                    C.c_int32, C.c_double, C.c_double, _P, _P, _P, C.POINTER(C.c_double), _P, _P, _P, _P]),
     "mfm_pt_exchange": (C.c_int, [_P, _U32, _U32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
@@ -432,6 +437,35 @@ class Context:
                                           _ptr(num_steps, I32), n_steps, int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
                                           _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(acc, F32), _ptr(is_acc, U8),
                                           _ptr(traj_pos, F32), _ptr(traj_logp, F64), _ptr(total_leapfrog, I64)))
+
+    # ---- microcanonical Langevin Monte Carlo (include/mfm.h: mfm_mclmc_*) ----
+    def mclmc_init(self, key, momentum):
+        """``mfm_mclmc_init``: the unit momenta ``momentum [n_chain_local, dim]`` (float64), chain b from ``split(key, n_chain_total)[chain_offset + b]``."""
+        _chk(self.lib.mfm_mclmc_init(self.h, int(key[0]), int(key[1]), _ptr(momentum, F64)))
+
+    def mclmc_step(self, key, beta, step_size, L, integrator, pos, logp, grad, momentum, energy_change=None, kinetic_change=None):
+        """``mfm_mclmc_step``: one MCLMC step of every local chain (``integrator`` 0: leapfrog, 1: McLachlan; ``L``: the momentum
+        decoherence length, ``inf`` for none), state ``(pos, logp, grad, momentum)`` updated in place; the two infos are float64 ``[n_chain_local]``."""
+        _chk(self.lib.mfm_mclmc_step(self.h, int(key[0]), int(key[1]), float(beta), float(step_size), float(L), int(integrator),
+                                     _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64), _ptr(energy_change, F64), _ptr(kinetic_change, F64)))
+
+    def mclmc_step_keys(self, keys, beta, step_size, L, integrator, pos, logp, grad, momentum, energy_change=None, kinetic_change=None):
+        """``mfm_mclmc_step_keys``: ``keys`` is an int32/uint32 device tensor [n_chain_local, 2], one key per chain."""
+        _chk(self.lib.mfm_mclmc_step_keys(self.h, _ptr(keys, I32), float(beta), float(step_size), float(L), int(integrator),
+                                          _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64), _ptr(energy_change, F64), _ptr(kinetic_change, F64)))
+
+    def mclmc_run(self, key, beta, step_size, L, integrator, n_steps, pos, logp, grad, momentum, thin=0, de_sum=None, de_sumsq=None,
+                  n_nonfinite=None, energy_trace=None, traj_pos=None, traj_logp=None, key_mode=None):
+        """``mfm_mclmc_run``: ``n_steps`` MCLMC steps in one launch, state updated in place; ``key`` / ``key_mode`` and the trajectory as
+        ``hmc_run``'s.  Per chain (optional): ``de_sum`` / ``de_sumsq`` float64, the sums of the steps' energy changes and of their
+        squares, ``n_nonfinite`` int32, the steps whose energy change is not finite; ``energy_trace`` float64 ``[n_steps, n_chain_local]``."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_mclmc_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size), float(L),
+                                    int(integrator), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64),
+                                    _ptr(de_sum, F64), _ptr(de_sumsq, F64), _ptr(n_nonfinite, I32), _ptr(energy_trace, F64),
+                                    _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
 
     def chees_warmup(self, key, beta, step0, n_iter, pos, logp, grad, traj0=None, n_valid=None, target_accept=0.651, learning_rate=0.025,
                      max_leapfrog=1000, decay=0.5, divergence_threshold=1000.0, trace=None, prop=None, vel=None, alpha=None, key_mode=None,

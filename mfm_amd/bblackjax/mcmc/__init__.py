@@ -1,2 +1,3 @@
 from . import nuts  # noqa: F401
 from . import elliptical_slice  # noqa: F401
+from . import mclmc  # noqa: F401

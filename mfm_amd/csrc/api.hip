@@ -16,6 +16,7 @@
 #include "lgcp.hip"
 #include "hmc.hip"
 #include "hmc_run.hip"
+#include "mclmc.hip"
 #include "nuts.hip"
 #include "warmup.hip"
 #include "nuts_warmup.hip.h"
@@ -940,6 +941,84 @@ extern "C" int mfm_hmc_run_lengths(mfm_ctx* x, int key_mode, uint32_t k0, uint32
   r.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
   ProfScope ps_(x, PROF_MALA);
   if (launch_hmc_run_lengths(r, d_num_steps, d_total_leapfrog, x->stream)) return too_large(x, "HMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+
+// Microcanonical Langevin Monte Carlo (mclmc.hip).  Checks in mfm_hmc_run's order, then the sampler's own: a rejected call touches nothing.
+static double mclmc_refresh_scale(double step, double L, int dim) {      // nu (mclmc.hip); L = +inf: exp(0) - 1 = 0 exactly
+  return std::sqrt((std::exp(2.0 * step / L) - 1.0) / (double)dim);
+}
+static int mclmc_check(mfm_ctx* x, double step, double L, int integrator) {
+  CHECKED(hmc_refuse_cox(x));
+  if (!x->h_inv_mass.empty()) return fail(MFM_EUNSUPPORTED, "MCLMC runs at unit mass: remove the installed inverse mass (mfm_hmc_set_inverse_mass with n = 0)");
+  if (x->cfg.dim < 2) return fail(MFM_EINVAL, "dim must be at least 2 for MCLMC (got %d): the momentum lives on the unit sphere", x->cfg.dim);
+  if (!(step > 0) || std::isinf(step)) return fail(MFM_EINVAL, "step_size must be positive and finite (got %g)", step);
+  if (!(L > 0)) return fail(MFM_EINVAL, "L must be positive, +inf for no momentum refresh (got %g)", L);
+  if (!std::isfinite(mclmc_refresh_scale(step, L, x->cfg.dim)))
+    return fail(MFM_EINVAL, "L = %g is too small for step_size %g: the refresh scale sqrt((exp(2 step_size / L) - 1) / dim) is not finite", L, step);
+  if (integrator != 0 && integrator != 1) return fail(MFM_EINVAL, "integrator must be 0 (leapfrog) or 1 (McLachlan) (got %d)", integrator);
+  return MFM_OK;
+}
+static MclmcArgs mclmc_args(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double L, int integrator,
+                            float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_de, double* d_dk) {
+  MclmcArgs a; memset(&a, 0, sizeof a);
+  a.T = x->net.T; a.key = Key2{k0, k1}; a.keys = d_keys; a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local;
+  a.beta = beta;
+  // the schedule's coefficient table (tests/mclmc_ref.py: SCHEDULES): leapfrog B A B, McLachlan's minimal-norm scheme B A B A B
+  const double b1 = 0.1931833275037836;
+  if (integrator == 0) { a.n_stages = 1; a.hb[0] = 0.5 * step; a.hb[1] = 0.5 * step; a.ha[0] = 1.0 * step; }
+  else { a.n_stages = 2; a.hb[0] = b1 * step; a.hb[1] = (1.0 - 2.0 * b1) * step; a.hb[2] = b1 * step; a.ha[0] = 0.5 * step; a.ha[1] = 0.5 * step; }
+  a.nu = mclmc_refresh_scale(step, L, x->cfg.dim);
+  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.mom = d_mom; a.energy_change = d_de; a.kinetic_change = d_dk;
+  return a;
+}
+extern "C" int mfm_mclmc_init(mfm_ctx* x, uint32_t k0, uint32_t k1, double* d_momentum) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_momentum) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(hmc_refuse_cox(x));
+  if (x->cfg.dim < 2) return fail(MFM_EINVAL, "dim must be at least 2 for MCLMC (got %d): the momentum lives on the unit sphere", x->cfg.dim);
+  ProfScope ps_(x, PROF_MALA);
+  launch_mclmc_init(Key2{k0, k1}, (uint32_t)x->cfg.n_chain_total, (uint32_t)x->cfg.chain_offset, x->cfg.n_chain_local, x->cfg.dim, d_momentum, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+static int mclmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double L, int integrator,
+                             float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_de, double* d_dk) {
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad || !d_mom) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(mclmc_check(x, step, L, integrator));
+  const MclmcArgs a = mclmc_args(x, k0, k1, d_keys, beta, step, L, integrator, d_pos, d_logp, d_grad, d_mom, d_de, d_dk);
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_mclmc_step(a, x->stream)) return too_large(x, "MCLMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += x->cfg.n_chain_local;      // (steps only, as mfm_hmc_step)
+  return MFM_OK;
+}
+extern "C" int mfm_mclmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, double L, int integrator, float* d_pos, double* d_logp,
+                              float* d_grad, double* d_mom, double* d_de, double* d_dk) { use_ctx(x);
+  return mclmc_step_common(x, k0, k1, nullptr, beta, step, L, integrator, d_pos, d_logp, d_grad, d_mom, d_de, d_dk);
+}
+extern "C" int mfm_mclmc_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, double step, double L, int integrator, float* d_pos, double* d_logp,
+                                   float* d_grad, double* d_mom, double* d_de, double* d_dk) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return mclmc_step_common(x, 0, 0, d_keys, beta, step, L, integrator, d_pos, d_logp, d_grad, d_mom, d_de, d_dk);
+}
+extern "C" int mfm_mclmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double L, int integrator,
+                             int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_de_sum,
+                             double* d_de_sumsq, int32_t* d_n_nonfinite, double* d_energy_trace, float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad || !d_mom) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  CHECKED(mclmc_check(x, step, L, integrator));
+  MclmcRunArgs r; memset(&r, 0, sizeof r);
+  r.m = mclmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, L, integrator, d_pos, d_logp, d_grad, d_mom, nullptr, nullptr);
+  r.t = RunTail{key_mode, n_steps, thin, nullptr, nullptr, d_traj_pos, d_traj_logp};
+  r.de_sum = d_de_sum; r.de_sumsq = d_de_sumsq; r.n_nonfinite = d_n_nonfinite; r.energy_trace = d_energy_trace;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_mclmc_run(r, x->stream)) return too_large(x, "MCLMC");
   LAUNCHCHK();
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
   return MFM_OK;

@@ -28,6 +28,7 @@ struct MalaRunArgs {
 __device__ __attribute__((noinline)) double run_normal64(Key2 key, uint32_t idx, uint32_t size) { return normal64(key, idx, size); }
 __device__ __attribute__((noinline)) double run_uniform01(Key2 key) { return uniform01(key, 0, 1); }
 __device__ __attribute__((noinline)) double run_exp(double v) { return exp(v); }
+__device__ __attribute__((noinline)) double run_sqrt(double v) { return sqrt(v); }      // (mclmc.hip)
 struct RunExp { __device__ __forceinline__ double operator()(double v) const { return run_exp(v); } };
 
 // The resident chain's registers and a step's outcome, as mala_resident_step sees them (HmcResident's counterpart, hmc_run.hip)

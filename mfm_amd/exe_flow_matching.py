@@ -225,6 +225,27 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
     hmc_step = eng.ctx.cox_hmc_step if getattr(dist, "kind", None) == "lgcp" else eng.ctx.hmc_step      # (by target, as bblackjax.mcmc.hmc)
     if use_nuts:
         info["nuts_acc"] = t.empty(n, device=eng.dev, dtype=t.float64)
+    use_mclmc = getattr(args, "mcmc_kernel", "mala") == "mclmc"
+    if use_mclmc:
+        from .bblackjax.mcmc.mclmc import integrator_id
+        mclmc_integrator = integrator_id(getattr(args, "mclmc_integrator", "mclachlan"))
+        info["mclmc_de"] = t.empty(n, device=eng.dev, dtype=t.float64)
+        eng.mclmc_momentum = None                      # [n, d] float64 unit momenta, drawn at the first MCLMC step and kept by the engine
+        eng.mclmc_energy = t.zeros(2, device=eng.dev, dtype=t.float64)      # sum dE, sum dE^2 over the run's MCLMC steps (this rank's chains)
+        eng.mclmc_energy_count = 0                     # ... and how many terms they hold (host: n_valid per step)
+
+    def mclmc_train_step(rng_key, beta, pos, logp, grad):
+        """Build-side mode (--mcmc_kernel mclmc): one MCLMC step (mfm_mclmc_step).  It always moves; a flow step between two of them
+        replaces x and keeps u, which is valid: the stationary law is p(x) x uniform(u)."""
+        if eng.mclmc_momentum is None:
+            eng.mclmc_momentum = t.empty(pos.shape, device=eng.dev, dtype=t.float64)
+            eng.ctx.mclmc_init(jr.split(rng_key)[1], eng.mclmc_momentum)
+        de = info["mclmc_de"]
+        eng.ctx.mclmc_step(rng_key, beta, args.step_size, mclmc_L(args), mclmc_integrator, pos, logp, grad, eng.mclmc_momentum, energy_change=de)
+        v = de[:eng.n_valid]
+        eng.mclmc_energy += t.stack([v.sum(), (v * v).sum()])
+        eng.mclmc_energy_count += int(eng.n_valid)
+        info["acc"].fill_(1); info["isacc"].fill_(1)
 
     def train_data_generator(rng_key, states, count, vector_field_param=None, beta=1.0):
         """:300-314.  States are updated IN PLACE (and returned); infos are views of reused device buffers."""
@@ -244,6 +265,8 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
         elif use_nuts:         # build-side mode (--mcmc_kernel nuts): a No-U-turn transition (mfm_nuts_step); it always takes its tree's proposal
             eng.ctx.nuts_step(rng_key, beta, args.step_size, int(getattr(args, "max_tree_depth", 10)), pos, logp, grad, acceptance_rate=info["nuts_acc"])
             info["acc"].copy_(info["nuts_acc"]); info["isacc"].fill_(1)
+        elif use_mclmc:
+            mclmc_train_step(rng_key, beta, pos, logp, grad)
         else:
             eng.ctx.mala_step(rng_key, beta, args.step_size, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["w"])
         return MALAState(pos, logp, grad), MALAInfo(info["acc"], info["isacc"], info["prop"], info["w"])
@@ -259,7 +282,7 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
     train_data_generator.info_buffers = info
     # what run() needs to issue generator + train_step as ONE library call (mfm_train_iter) where that is the same computation
     train_data_generator.flow_mode = mode
-    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc and not use_nuts
+    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc and not use_nuts and not use_mclmc
     return train_data_generator, init_fn, transform_and_logdet
 
 
@@ -325,6 +348,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         raise ValueError("mcmc_per_flow_steps < 0 trains on exact samples and needs a target with sample_model (:382-386)")
     check_adapt_args(args)                                                                  # --adapt_steps (build-side addition)
     check_cox_args(dist, args)                                                              # --example pines: what its HMC kernel does not serve
+    check_mclmc_args(args)                                                                  # --mcmc_kernel mclmc: --mclmc_L, --mclmc_integrator
     learning_iter = args.learning_iter
     iter_per_temp = args.anneal_iter // args.num_anneal_temp                                # :330
     n_iter, n_chain = args.eval_iter, args.num_chain
@@ -369,7 +393,11 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     train_states = init_fn(pos0, beta)                                                      # :431
     adapt_start = time.time()
     adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
-    if adapt_stats:
+    if "adapted_L" in adapt_stats:                                                          # (--mcmc_kernel mclmc)
+        logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']}, L= {adapt_stats['adapted_L']} (energy variance per dimension= {adapt_stats['adapt_energy_var']})")
+        wandb.log(adapt_stats)
+        train_start += time.time() - adapt_start
+    elif adapt_stats:
         logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']} (mean acceptance probability over the warmup= {adapt_stats['adapt_acceptance']})")
         if "adapted_trajectory_length" in adapt_stats:                                      # (--hmc_adapt chees)
             logger.info(f"Adapted trajectory length= {adapt_stats['adapted_trajectory_length']} (mean leapfrog steps per iteration= {adapt_stats['adapt_mean_leapfrog']:.4g})")
@@ -454,8 +482,26 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
         logger.info(f"Max mean disc of exact samples= {mmd_}")
     else:
         mmd = mmd_ = 0.0                                                                    # :490
+    mclmc_stats = {}
+    if getattr(args, "mcmc_kernel", "mala") == "mclmc" and not use_real_samples:            # the energy error of the run's own MCLMC steps
+        from .engine import allreduce_sum_
+        count = torch.tensor([float(eng.mclmc_energy_count)], device=eng.dev, dtype=torch.float64)      # (once, after the loop)
+        e = allreduce_sum_(torch.cat([eng.mclmc_energy, count]))[0].tolist()
+        m = e[0] / e[2] if e[2] else float("nan")
+        mclmc_stats = dict(energy_var_per_dim=(e[1] / e[2] - m * m) / args.dim if e[2] else float("nan"))
+        logger.info(f"MCLMC energy variance per dimension over the run= {mclmc_stats['energy_var_per_dim']:.4g}")
+        wandb.log(mclmc_stats)
     ess_stats = chain_ess_per_step(eng, dist, args, train_states, key_gen)                  # --ess_steps (build-side addition; {} at 0)
-    if ess_stats:
+    if ess_stats and getattr(args, "mcmc_kernel", "mala") == "mclmc":
+        logger.info("ESS per MCLMC step (min, median, mean over chains and coordinates)= "
+                    + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_step_min", "ess_per_step_median", "ess_per_step_mean")))
+        logger.info("ESS per gradient evaluation of the MCLMC kernel (min, median, mean)= "
+                    + ", ".join(f"{ess_stats[k]:.4g}" for k in ("ess_per_grad_min", "ess_per_grad_median", "ess_per_grad_mean")))
+        logger.info(f"Split R-hat across chains (max, median over coordinates)= {ess_stats['rhat_max']:.4g}, {ess_stats['rhat_median']:.4g}")
+        logger.info("Multi-chain ESS per gradient evaluation of the MCLMC kernel and chain (min, median, mean)= "
+                    + ", ".join(f"{ess_stats['ess_multichain_per_grad_' + k]:.4g}" for k in ("min", "median", "mean")))
+        wandb.log(ess_stats)
+    elif ess_stats:
         use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
         use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
         step_name = (f"HMC step ({ess_stats['hmc_mean_leapfrog']:.4g} leapfrog steps on average)" if "hmc_mean_leapfrog" in ess_stats
@@ -481,7 +527,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     if return_extras:
         return res, res_, dict(metrics=metrics.cpu().numpy(), betas=np.array(betas), lrs=np.array(lrs), states=train_states,
                                engine=eng, state=state, flow_samples=flow_samples, exact_samples=exact_samples, model=model,
-                               final=fin, key_gen=key_gen, **ess_stats, **adapt_stats)
+                               final=fin, key_gen=key_gen, **ess_stats, **adapt_stats, **mclmc_stats)
     eng.close()
     return res, res_
 
@@ -496,7 +542,10 @@ def check_adapt_args(args):
         raise ValueError("--adapt_mass adapts the mass matrix during the --adapt_steps N warmup steps: give N > 0")
     if n_steps > 0 and args.mcmc_per_flow_steps < 0:
         raise ValueError("--adapt_steps has nothing to adapt with mcmc_per_flow_steps < 0: that run trains on exact samples and takes no MCMC step")
-    if n_steps > 0 and getattr(args, "mcmc_kernel", "mala") not in ("hmc", "nuts"):
+    kern = getattr(args, "mcmc_kernel", "mala")
+    if kern == "mclmc" and getattr(args, "adapt_mass", False):
+        raise ValueError("--adapt_mass is not served with --mcmc_kernel mclmc: the MCLMC kernel (mfm_mclmc_*) runs at unit metric")
+    if n_steps > 0 and kern not in ("hmc", "nuts", "mclmc"):
         raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
                          "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
     hmc_adapt = getattr(args, "hmc_adapt", "dual")
@@ -525,6 +574,8 @@ def check_cox_args(dist, args):
     kern = getattr(args, "mcmc_kernel", "mala")
     if getattr(args, "do_pt", False):
         raise ValueError("--do_pt is not served with --example pines: parallel tempering (mfm_pt_run) has no local move for the Cox process")
+    if kern == "mclmc":
+        raise ValueError("--mcmc_kernel mclmc is not served with --example pines: MCLMC (mfm_mclmc_*) has no Cox process kernel (use --mcmc_kernel hmc)")
     if kern == "nuts":
         raise ValueError("--mcmc_kernel nuts is not served with --example pines: the No-U-turn sampler has no Cox process kernel (use --mcmc_kernel hmc)")
     if getattr(args, "adapt_mass", False):
@@ -534,6 +585,22 @@ def check_cox_args(dist, args):
                          "(use the default --hmc_adapt dual)")
     if kern == "hmc" and int(getattr(dist, "dim", 0)) > 1024:
         raise ValueError(f"--mcmc_kernel hmc with --example pines serves dim <= 1024, a 32 x 32 grid (got {dist.dim}): give --force_dim")
+
+
+def check_mclmc_args(args):
+    """``--mcmc_kernel mclmc``'s own flags, before any device work: ``--mclmc_L`` (0 or positive) and ``--mclmc_integrator``."""
+    if getattr(args, "mcmc_kernel", "mala") != "mclmc":
+        return
+    if float(getattr(args, "mclmc_L", 0.0) or 0.0) < 0:
+        raise ValueError(f"--mclmc_L must be positive, or 0 for sqrt(dim) (got {args.mclmc_L})")
+    from .bblackjax.mcmc.mclmc import integrator_id
+    integrator_id(getattr(args, "mclmc_integrator", "mclachlan"))
+
+
+def mclmc_L(args):
+    """``--mclmc_L``: the momentum decoherence length of ``--mcmc_kernel mclmc``; 0 (the default) means ``sqrt(dim)``."""
+    L = float(getattr(args, "mclmc_L", 0.0) or 0.0)
+    return L if L > 0 else float(np.sqrt(args.dim))
 
 
 def hmc_num_steps(args, i):
@@ -575,6 +642,20 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     n_steps = check_adapt_args(args)
     if n_steps <= 0:
         return {}
+    if getattr(args, "mcmc_kernel", "mala") == "mclmc":
+        # --mcmc_kernel mclmc: mclmc_find_L_and_step_size over N steps on the copy, from --step_size; args.step_size and args.mclmc_L are set
+        from .bblackjax.adaptation.mclmc_adaptation import mclmc_find_L_and_step_size
+        from .bblackjax.mcmc.mclmc import mclmc
+        integ = getattr(args, "mclmc_integrator", "mclachlan")
+        make = lambda L, eps: mclmc(dist.logprob, L, eps, integ)
+        k_init, k_tune = jr.split(jr.split(key_gen, 4)[3])
+        history = []
+        _, params = mclmc_find_L_and_step_size(make, make(1.0, 1.0).init(pos0.clone(), k_init), k_tune, n_steps, initial_step_size=args.step_size,
+                                               n_valid=eng.n_valid, ess_fn=lambda p: mcmc_utils_ess(p, eng), history=history)
+        args.step_size, args.mclmc_L = params.step_size, params.L
+        # adapt_energy_var: the variance per dimension of the LAST step-size round, the one the returned step size was derived from (at the
+        # phase-2 L; the phase-3 run that follows only replaces L)
+        return dict(adapted_step_size=params.step_size, adapted_L=params.L, adapt_energy_var=[h for h in history if h[0] != 3][-1][3])
     from .bblackjax.mcmc.hmc import hmc
     from .engine import global_mean_std
     if getattr(args, "hmc_adapt", "dual") == "chees":
@@ -622,6 +703,11 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
     return dict(adapted_step_size=info.pooled_step_size, adapt_acceptance=acc.item())
 
 
+def mcmc_utils_ess(positions, eng):
+    from . import mcmc_utils
+    return mcmc_utils.effective_sample_size(positions, ctx=eng.ctx)
+
+
 def chain_ess_per_step(eng, dist, args, states, key_gen):
     """``--ess_steps N``: N steps of the kernel the run trained with (``--mcmc_kernel``: MALA steps, or HMC steps of ``--hmc_steps``
     leapfrog steps) at ``--step_size`` from the final chains at beta = 1 in one launch (``kernel.run``, ``thin = 1``) and Geyer's
@@ -635,7 +721,10 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     ``ess_multichain_per_grad_*``).
     ``--mcmc_kernel nuts``: N No-U-turn transitions (``nuts(...).step.run``); a transition costs its tree's leapfrog steps, so ``ess_per_grad_*``
     and ``ess_multichain_per_grad_*`` divide by the MEASURED mean leapfrog count per transition over the run and the chains of all ranks,
-    logged as ``nuts_mean_leapfrog`` beside ``nuts_mean_depth`` and ``nuts_divergent`` (the number of divergent transitions)."""
+    logged as ``nuts_mean_leapfrog`` beside ``nuts_mean_depth`` and ``nuts_divergent`` (the number of divergent transitions).
+    ``--mcmc_kernel mclmc``: N MCLMC steps (``mclmc(...).step.run``) at ``--step_size`` / ``--mclmc_L`` from the final chains with fresh unit
+    momenta (the key's two halves: momenta, run); a step costs 1 (leapfrog) or 2 (McLachlan) gradient evaluations, which ``ess_per_grad_*`` and
+    ``ess_multichain_per_grad_*`` divide by; ``energy_var_per_dim_ess_run`` is that run's energy-change variance per dimension."""
     n_steps = int(getattr(args, "ess_steps", 0) or 0)
     if n_steps <= 0 or states.logdensity is None:                  # (training on exact samples keeps no MCMC state)
         return {}
@@ -643,25 +732,37 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     from . import mcmc_utils
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
     use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
-    if use_hmc:
+    use_mclmc = getattr(args, "mcmc_kernel", "mala") == "mclmc"
+    # the kernel, the state it starts from, its key and what a step costs in gradient evaluations ...
+    key, run_kw = jr.split(key_gen, 3)[2], {}
+    if use_mclmc:          # fresh unit momenta from one half of the key, the run on the other; 1 (leapfrog) or 2 (McLachlan) gradients per step
+        from .bblackjax.mcmc.mclmc import integrator_id, mclmc
+        integ = integrator_id(getattr(args, "mclmc_integrator", "mclachlan"))
+        algo = mclmc(dist.logprob, mclmc_L(args), args.step_size, integ)
+        k_init, key = jr.split(key)
+        start, grads_per_step = algo.init(states.position, k_init), float(integ + 1)
+    elif use_hmc:
         from .bblackjax.mcmc.hmc import hmc
         algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps), getattr(args, "inverse_mass_matrix", None))      # (--adapt_mass)
+        start, grads_per_step = algo.init(states.position), float(int(args.hmc_steps))
     elif use_nuts:
         from .bblackjax.mcmc.nuts import nuts
         algo = nuts(dist.logprob, args.step_size, int(getattr(args, "max_tree_depth", 10)), getattr(args, "inverse_mass_matrix", None))
+        start, grads_per_step = algo.init(states.position), 1.0      # (replaced by the measured leapfrog count below)
     else:
         from .bblackjax.mcmc.mala import mala
         algo = mala(dist.logprob, args.step_size)
+        start, grads_per_step = algo.init(states.position), 1.0
     chees = use_hmc and getattr(args, "hmc_trajectory_length", None) is not None          # (--hmc_adapt chees: the jittered leapfrog counts)
     if chees:
-        _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1,
-                                num_integration_steps_per_step=lambda i: hmc_num_steps(args, i))
-    else:
-        _, info = algo.step.run(jr.split(key_gen, 3)[2], algo.init(states.position), n_steps, thin=1)
+        run_kw["num_integration_steps_per_step"] = lambda i: hmc_num_steps(args, i)
+    # ... and the run, the same call for every kernel
+    _, info = algo.step.run(key, start, n_steps, thin=1, **run_kw)
     ess, _ = mcmc_utils.effective_sample_size(info.positions[:, :eng.n_valid], ctx=eng.ctx)
     per_step = (ess.double() / n_steps).reshape(-1)
     out = dict(ess_per_step_min=per_step.min().item(), ess_per_step_median=per_step.median().item(), ess_per_step_mean=per_step.mean().item())
-    grads_per_step = float(int(args.hmc_steps)) if use_hmc else 1.0
+    if use_mclmc:
+        out["energy_var_per_dim_ess_run"] = info.energy_var_per_dim
     if chees:          # the measured mean leapfrog count per step (the same for every chain), as NUTS
         grads_per_step = info.num_leapfrog / n_steps
         out["hmc_mean_leapfrog"] = grads_per_step
@@ -672,7 +773,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
         means = [global_mean_std(per_chain[:, q].contiguous(), eng.n_total)[0].item() for q in range(3)]
         grads_per_step = means[0]
         out.update(nuts_mean_leapfrog=means[0], nuts_mean_depth=means[1], nuts_divergent=int(round(means[2] * eng.n_total)))
-    if use_hmc or use_nuts:
+    if use_hmc or use_nuts or use_mclmc:
         for name in ("min", "median", "mean"):
             out["ess_per_grad_" + name] = out["ess_per_step_" + name] / grads_per_step
     # across the chains (of all ranks): split-R-hat and the multi-chain ESS, per step and chain (diagnostics.py; a chain stuck in one
@@ -682,7 +783,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     rhat, multi = cd.rhat.double(), cd.ess.double() / (float(eng.n_total) * n_steps)
     out.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item(), ess_multichain_per_step_min=multi.min().item(),
                ess_multichain_per_step_median=multi.median().item(), ess_multichain_per_step_mean=multi.mean().item())
-    if use_hmc or use_nuts:
+    if use_hmc or use_nuts or use_mclmc:
         for name in ("min", "median", "mean"):
             out["ess_multichain_per_grad_" + name] = out["ess_multichain_per_step_" + name] / grads_per_step
     return out

@@ -214,7 +214,7 @@ def check_pt_args(args):
         raise ValueError("--do_pt runs alone: not with --do_smc or --do_svgd")
     kern = getattr(args, "mcmc_kernel", "mala")
     if kern not in ("mala", "hmc"):
-        raise ValueError(f"--do_pt takes --mcmc_kernel mala or hmc as the local move (got {kern}: NUTS is not served)")
+        raise ValueError(f"--do_pt takes --mcmc_kernel mala or hmc as the local move (got {kern}: NUTS and MCLMC are not served)")
     if K < 2 or int(args.num_chain) % K:
         raise ValueError(f"--do_pt: num_chain ({args.num_chain}) must be a multiple of --pt_temps ({K} >= 2): chains are R ladders of K temperatures")
     return K, int(args.num_chain) // K

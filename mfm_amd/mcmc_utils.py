@@ -40,12 +40,15 @@ def inference_loop0(rng, init_state, kernel, n_iter):
     ``states`` holds the state AFTER each of the ``n_iter`` steps along a leading axis.  With a kernel that carries ``.run`` the
     per-step gradients are not kept (``states.logdensity_grad is None``) and ``info`` is the run's ``MALARunInfo`` / ``HMCRunInfo``
     (acceptance per chain over the run, the last step's ``MALAInfo`` / ``HMCInfo``; any tuple with ``positions`` and
-    ``logdensities`` serves) rather than ``n_iter`` stacked infos."""
+    ``logdensities`` serves) rather than ``n_iter`` stacked infos.  The stacked states are ``type(init_state)(positions, logdensities,
+    None)``, the three fields of ``MALAState``; a state type with other fields gives a classmethod ``from_run(info)`` that builds them
+    (``mclmc``'s four-field ``IntegratorState``: positions and log-densities, momenta and gradients ``None``)."""
     n_iter = int(n_iter)
     run = getattr(kernel, "run", None)
     if run is not None:
         _, info = run(rng, init_state, n_iter, thin=1)
-        return type(init_state)(info.positions, info.logdensities, None), info
+        from_run = getattr(type(init_state), "from_run", None)      # (a state with more fields than MALAState's three builds itself: mclmc's IntegratorState)
+        return (from_run(info) if from_run else type(init_state)(info.positions, info.logdensities, None)), info
     if n_iter < 1:
         raise ValueError(f"n_iter must be at least 1 (got {n_iter})")
     keys = jr.split(rng, n_iter)
