@@ -316,6 +316,80 @@ int mfm_mclmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, cons
                   float* d_pos, double* d_logp, float* d_grad, double* d_momentum,
                   double* d_de_sum, double* d_de_sumsq, int32_t* d_n_nonfinite, double* d_energy_trace,
                   float* d_traj_pos, double* d_traj_logp);
+/* GENERALIZED HMC WITH PERSISTENT MOMENTUM (GHMC: Horowitz 1991, with the non-reversible slice accept; Hoffman & Sountsov 2022;
+ * blackjax.ghmc) -- a BUILD-SIDE MODE like mfm_hmc_*; tests/ghmc_ref.py restates it in float64 and is the definition.  A chain is
+ * (d_pos, d_logp, d_grad) as mfm_mala_init leaves them plus a momentum d_momentum, double[n_chain_local][dim], and a slice variable
+ * d_slice, double[n_chain_local], in (-1, 1).  Parameters: step_size eps > 0, alpha in (0, 1], delta >= 0, and d_inverse_mass, DEVICE
+ * double[dim], the diagonal of the inverse mass matrix minv (NULL: unit metric).  The mass is the CALL's argument: the inverse mass
+ * installed by mfm_hmc_set_inverse_mass is not read.  One transition, with the chain key kb:
+ *   1. p <- sqrt(1 - alpha) p + sqrt(alpha) n / sqrt(minv), n_j = normal64(split(kb, 2)[0], j, dim), the draw of mfm_hmc_step
+ *   2. s <- fmod(s + 1 + delta, 2) - 1 (a deterministic drift)
+ *   3. H_0 = -logp + 1/2 sum_j minv_j p_j^2
+ *   4. ONE velocity-Verlet step as mfm_hmc_step makes it: half kick p += eps/2 g, drift x <- (float)(x + eps minv p), value and
+ *      gradient at x, half kick
+ *   5. H_1 likewise; dH = H_1 - H_0
+ *   6. accept iff |s| <= exp(-dH); a NaN dH rejects.  Accepted: the state becomes the end point, p <- p_end, s <- s exp(dH).
+ *      Rejected: x, logp and grad are kept, p <- -p (the REFRESHED momentum of 1., negated), s is kept
+ *   7. info: acceptance_rate = min(1, exp(-dH)) (float), is_accepted (uint8), energy_change = dH (double); each [B], may be null
+ * At alpha = 1 the proposal and acceptance_rate have the bits of mfm_hmc_step_keys at num_steps = 1 on the same keys (with an installed
+ * inverse mass equal to d_inverse_mass: of its mass instances).  The calls only enqueue; shards (n_chain_total != n_chain_local) are served.
+ * Checks, in this order, a rejected call touching nothing: state pointers (and keys / key_mode / n_steps / thin as mfm_hmc_run);
+ * MFM_EUNSUPPORTED for the Cox process (mfm_hmc_step's message); MFM_EINVAL naming the argument for step_size not positive, alpha
+ * outside (0, 1], delta negative or NaN.
+ * mfm_ghmc_init: with kb = split(key, n_chain_total)[chain_offset + b], p_j = normal64(split(kb, 2)[0], j, dim) / sqrt(minv_j) and
+ * s = 2 uniform(split(kb, 2)[1]) - 1. */
+int mfm_ghmc_init(mfm_ctx* ctx, uint32_t key0, uint32_t key1, const double* d_inverse_mass, double* d_momentum, double* d_slice);
+/* one transition; chain b uses split(key, n_chain_total)[chain_offset + b] (or d_keys[b]) */
+int mfm_ghmc_step(mfm_ctx* ctx, uint32_t key0, uint32_t key1, double beta, double step_size, double alpha, double delta,
+                  const double* d_inverse_mass, float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_slice,
+                  float* d_acceptance_rate, uint8_t* d_is_accepted, double* d_energy_change);
+int mfm_ghmc_step_keys(mfm_ctx* ctx, const uint32_t* d_keys, double beta, double step_size, double alpha, double delta,
+                       const double* d_inverse_mass, float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_slice,
+                       float* d_acceptance_rate, uint8_t* d_is_accepted, double* d_energy_change);
+/* n_steps transitions in ONE launch, x, g, logp, p and s resident in registers, bit-identical with n_steps single-step calls; key_mode,
+ * the step keys, thin and the trajectory layout are mfm_hmc_run's.  Optional outputs (NULL to skip): d_n_accepted int32[B]; d_acc_sum
+ * double[B], the sum of the acceptance rates; d_energy_sum double[B], the sum of dH over the ACCEPTED steps in step order; the three
+ * infos of the LAST step. */
+int mfm_ghmc_run(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                 double beta, double step_size, double alpha, double delta, const double* d_inverse_mass, int32_t n_steps, int32_t thin,
+                 float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_slice,
+                 int32_t* d_n_accepted, double* d_acc_sum, double* d_energy_sum,
+                 float* d_acceptance_rate, uint8_t* d_is_accepted, double* d_energy_change,
+                 float* d_traj_pos, double* d_traj_logp);
+/* MEADS WARMUP OF GHMC (Hoffman & Sountsov 2022; blackjax's meads_adaptation): n_iter GHMC transitions of ALL chains in which the step
+ * size, the diagonal inverse mass, alpha and delta are set from cross-chain statistics; tests/meads_ref.py restates it in float64 and is
+ * the definition.  The call only enqueues (six launches per iteration, ghmc.hip); the parameters live in device memory.
+ * n_valid chains form n_folds = K folds of m = n_valid / K (K >= 2, m >= 2, K m = n_valid <= n_chain_local); rows from n_valid on are
+ * stepped with fold 0's parameters and never read.  Chain perm[f m + i] is member i of fold f; perm starts as the identity and, with
+ * shuffle_every = S > 0, is replaced before iterations S + 1, 2 S + 1, ... by row r - 1 (r = 1, 2, ...) of d_perms, DEVICE
+ * int32[(n_iter - 1) / S][n_valid], permutations the HOST has drawn and uploaded before the call (bblackjax's meads_adaptation draws them
+ * with permutation_indices from a key); entries outside [0, n_valid) are clamped.  S = 0: never.
+ * Iteration t = 1 .. n_iter, for each fold f from the state BEFORE the step, in float64:
+ *   1. column mean mu_f and population standard deviation sd_f (ddof 0) of the fold's positions
+ *   2. Y = (x - mu_f) / sd_f and Z = grad sd_f, [m, dim] (Z not centred; both rounded to float32 for the Gram products), and
+ *      lam(X) = [ (sum_ij S_ij^2 - sum_i S_ii^2) / (m (m - 1)) ] / [ sum_i S_ii / m ], S = X X^T
+ *   3. eps_f = min(1, 0.5 / sqrt(lam(Z))), gamma_f = max(1 / sqrt(lam(Y)), 1 / (t eps_f)), alpha_f = 1 - exp(-2 eps_f gamma_f),
+ *      delta_f = alpha_f / 2, minv_f = sd_f^2
+ *   4. these become the parameters of fold (f + 1) mod K for this iteration's transition; if any of them is non-finite or eps_f <= 0
+ *      the receiving fold keeps its previous ones (before iteration 1: step0, unit mass, alpha0, alpha0 / 2)
+ * then one GHMC transition (mfm_ghmc_step) of every chain with its fold's parameters on the key mfm_hmc_run (n_steps = n_iter, same
+ * key_mode) uses for step t - 1: the bits of mfm_ghmc_step_keys with those parameters.  After the last iteration the same statistics
+ * are formed once over ALL n_valid chains with t = n_iter + 1: h_result (host, 3 doubles, or NULL) takes {eps, alpha, delta} and
+ * d_inverse_mass_out (double[dim], or NULL) sd^2.  With h_result the call ends by waiting for the stream; with NULL it makes no host
+ * synchronisation.  d_trace: double[n_iter][K][6] or NULL, per fold the eps, alpha, delta it USED, lam(Z) and lam(Y) it PRODUCED, its
+ * mean acceptance rate; d_mass_trace: double[n_iter][K][dim] or NULL, the minv it used.
+ * Checks, in this order: state pointers; key_mode / d_keys / n_iter as mfm_hmc_run; MFM_EUNSUPPORTED for the Cox process; MFM_EINVAL for
+ * step0 not positive, alpha0 outside (0, 1]; MFM_EUNSUPPORTED for a shard (n_chain_total != n_chain_local: the fold statistics would
+ * need an all-reduce); MFM_EINVAL for n_folds < 2, n_valid not a multiple of n_folds or giving m < 2 or above n_chain_local,
+ * shuffle_every < 0, d_perms missing when a shuffle falls inside n_iter. */
+int mfm_meads_warmup(mfm_ctx* ctx, int key_mode, uint32_t key0, uint32_t key1, const uint32_t* d_keys,
+                     double beta, double step0, double alpha0, int32_t n_iter, int32_t n_valid, int32_t n_folds,
+                     int32_t shuffle_every, const int32_t* d_perms,
+                     float* d_pos, double* d_logp, float* d_grad, double* d_momentum, double* d_slice,
+                     double* h_result, double* d_inverse_mass_out, double* d_trace, double* d_mass_trace);
+/* host only: h_out = {m, m_pad, d_pad, Gram workgroups per iteration} of a warmup (the fold size, its rows padded to the 64-row tile,
+ * dim padded to the 32-column chunk, 2 K T (T + 1) / 2 with T = m_pad / 64); MFM_EINVAL for what the warmup refuses */
+int mfm_meads_plan(int32_t n_valid, int32_t n_folds, int32_t dim, int32_t* h_out);
 /* ChEES-HMC WARMUP (Hoffman, Radul & Sountsov 2021; blackjax's chees_adaptation): n_iter HMC steps of ALL chains in which the step size
  * and the trajectory length are adapted ACROSS the chains; tests/chees_ref.py restates it in float64 and is the definition.  The call
  * only enqueues (four launches per iteration, chees.hip); eps_t, T_t, L_t and the optimizer's state live in device memory.

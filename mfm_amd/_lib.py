@@ -74,6 +74,14 @@ _SIGS = {
     "mfm_mclmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_int, _P, _P, _P, _P, _P, _P]),
     "mfm_mclmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P,
                                 _P, _P, _P, _P]),
+    "mfm_ghmc_init": (C.c_int, [_P, _U32, _U32, _P, _P, _P]),
+    "mfm_ghmc_step": (C.c_int, [_P, _U32, _U32, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_ghmc_step_keys": (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_ghmc_run": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_double, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mfm_meads_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                   _P, _P, _P, _P, _P, C.POINTER(C.c_double), _P, _P, _P]),
+    "mfm_meads_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "mfm_chees_warmup": (C.c_int, [_P, C.c_int, _U32, _U32, _P, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                    C.c_int32, C.c_double, C.c_double, _P, _P, _P, C.POINTER(C.c_double), _P, _P, _P, _P]),
     "mfm_pt_exchange": (C.c_int, [_P, _U32, _U32, C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P]),
@@ -240,6 +248,14 @@ def cox_hmc_launch_plan(dim):
     tpw, sm = C.c_int32(), C.c_int32()
     _chk(load().mfm_cox_hmc_launch_plan(int(dim), C.byref(tpw), C.byref(sm)))
     return tpw.value, sm.value
+
+
+def meads_plan(n_valid, n_folds, dim):
+    """``mfm_meads_plan`` (host only): ``(m, m_pad, d_pad, Gram workgroups per iteration)`` of a MEADS warmup -- the fold size, its rows
+    padded to the 64-row tile, ``dim`` padded to the 32-column chunk, and ``2 K T (T + 1) / 2`` with ``T = m_pad / 64``."""
+    out = (C.c_int32 * 4)()
+    _chk(load().mfm_meads_plan(int(n_valid), int(n_folds), int(dim), out))
+    return tuple(out)
 
 
 WGRAD_SLABS, WGRAD_STREAM_K, WGRAD_WIDE = 0, 1, 2     # mfm_wgrad_info: kind
@@ -466,6 +482,58 @@ class Context:
                                     int(integrator), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64),
                                     _ptr(de_sum, F64), _ptr(de_sumsq, F64), _ptr(n_nonfinite, I32), _ptr(energy_trace, F64),
                                     _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    # ---- generalized HMC with persistent momentum (include/mfm.h: mfm_ghmc_*) ----
+    def ghmc_init(self, key, momentum, slice_, inverse_mass=None):
+        """``mfm_ghmc_init``: the momenta ``momentum [n_chain_local, dim]`` (float64, ``n / sqrt(inverse_mass)``) and the slice variables
+        ``slice_ [n_chain_local]`` (float64, in (-1, 1)), chain b from ``split(key, n_chain_total)[chain_offset + b]``.  ``inverse_mass``:
+        a float64 device tensor ``[dim]`` or ``None`` (unit metric)."""
+        _chk(self.lib.mfm_ghmc_init(self.h, int(key[0]), int(key[1]), _ptr(inverse_mass, F64), _ptr(momentum, F64), _ptr(slice_, F64)))
+
+    def ghmc_step(self, key, beta, step_size, alpha, delta, pos, logp, grad, momentum, slice_, inverse_mass=None, acc=None, is_acc=None,
+                  energy_change=None):
+        """``mfm_ghmc_step``: one GHMC transition (one leapfrog step, persistent momentum, slice accept) of every local chain, state
+        ``(pos, logp, grad, momentum, slice_)`` updated in place; infos: ``acc`` float32, ``is_acc`` uint8, ``energy_change`` float64."""
+        _chk(self.lib.mfm_ghmc_step(self.h, int(key[0]), int(key[1]), float(beta), float(step_size), float(alpha), float(delta), _ptr(inverse_mass, F64),
+                                    _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64), _ptr(slice_, F64),
+                                    _ptr(acc, F32), _ptr(is_acc, U8), _ptr(energy_change, F64)))
+
+    def ghmc_step_keys(self, keys, beta, step_size, alpha, delta, pos, logp, grad, momentum, slice_, inverse_mass=None, acc=None, is_acc=None,
+                       energy_change=None):
+        """``mfm_ghmc_step_keys``: ``keys`` is an int32/uint32 device tensor [n_chain_local, 2], one key per chain."""
+        _chk(self.lib.mfm_ghmc_step_keys(self.h, _ptr(keys, I32), float(beta), float(step_size), float(alpha), float(delta), _ptr(inverse_mass, F64),
+                                         _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64), _ptr(slice_, F64),
+                                         _ptr(acc, F32), _ptr(is_acc, U8), _ptr(energy_change, F64)))
+
+    def ghmc_run(self, key, beta, step_size, alpha, delta, n_steps, pos, logp, grad, momentum, slice_, inverse_mass=None, thin=0, n_acc=None,
+                 acc_sum=None, energy_sum=None, acc=None, is_acc=None, energy_change=None, traj_pos=None, traj_logp=None, key_mode=None):
+        """``mfm_ghmc_run``: ``n_steps`` GHMC transitions in one launch, state updated in place; ``key`` / ``key_mode`` and the trajectory
+        as ``hmc_run``'s.  Per chain (optional): ``n_acc`` int32, ``acc_sum`` float64 (sum of the acceptance rates), ``energy_sum``
+        float64 (sum of dH over the accepted steps); ``acc`` / ``is_acc`` / ``energy_change``: the last step's infos."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        _chk(self.lib.mfm_ghmc_run(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step_size), float(alpha),
+                                   float(delta), _ptr(inverse_mass, F64), int(n_steps), int(thin), _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32),
+                                   _ptr(momentum, F64), _ptr(slice_, F64), _ptr(n_acc, I32), _ptr(acc_sum, F64), _ptr(energy_sum, F64),
+                                   _ptr(acc, F32), _ptr(is_acc, U8), _ptr(energy_change, F64), _ptr(traj_pos, F32), _ptr(traj_logp, F64)))
+
+    def meads_warmup(self, key, beta, step0, alpha0, n_iter, pos, logp, grad, momentum, slice_, n_folds=4, n_valid=None, shuffle_every=0, perms=None,
+                     inverse_mass_out=None, trace=None, mass_trace=None, key_mode=None, read_result=True):
+        """``mfm_meads_warmup``: ``n_iter`` GHMC transitions of all chains with the step size, the diagonal inverse mass, alpha and delta
+        set per fold from cross-chain statistics; state updated in place.  ``perms``: int32 device tensor ``[(n_iter - 1) //
+        shuffle_every, n_valid]`` (needed when a shuffle falls inside ``n_iter``).  Returns ``(eps, alpha, delta)`` of the closing pass
+        over all chains (``None`` with ``read_result=False``: no host synchronisation); ``inverse_mass_out`` float64 ``[dim]`` takes its
+        ``sd^2``, ``trace`` float64 ``[n_iter, n_folds, 6]``, ``mass_trace`` float64 ``[n_iter, n_folds, dim]``."""
+        per_chain = getattr(key, "ndim", 1) == 2
+        mode = int(per_chain) if key_mode is None else int(key_mode)
+        k0, k1 = (0, 0) if per_chain or key is None else (int(key[0]), int(key[1]))
+        res = (C.c_double * 3)() if read_result else None
+        _chk(self.lib.mfm_meads_warmup(self.h, mode, k0, k1, _ptr(key, I32) if per_chain else None, float(beta), float(step0), float(alpha0), int(n_iter),
+                                       int(pos.shape[0] if n_valid is None else n_valid), int(n_folds), int(shuffle_every), _ptr(perms, I32),
+                                       _ptr(pos, F32), _ptr(logp, F64), _ptr(grad, F32), _ptr(momentum, F64), _ptr(slice_, F64), res,
+                                       _ptr(inverse_mass_out, F64), _ptr(trace, F64), _ptr(mass_trace, F64)))
+        return tuple(res) if read_result else None
 
     def chees_warmup(self, key, beta, step0, n_iter, pos, logp, grad, traj0=None, n_valid=None, target_accept=0.651, learning_rate=0.025,
                      max_leapfrog=1000, decay=0.5, divergence_threshold=1000.0, trace=None, prop=None, vel=None, alpha=None, key_mode=None,

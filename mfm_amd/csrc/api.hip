@@ -17,6 +17,7 @@
 #include "hmc.hip"
 #include "hmc_run.hip"
 #include "mclmc.hip"
+#include "ghmc.hip"
 #include "nuts.hip"
 #include "warmup.hip"
 #include "nuts_warmup.hip.h"
@@ -114,6 +115,7 @@ struct mfm_ctx {
   void* ac_ws = nullptr; size_t ac_ws_cap = 0;     // mfm_autocorr: the series means when the caller passes no d_mean
   void* cs_ws = nullptr; size_t cs_ws_cap = 0;     // mfm_chain_sums: mean and A_0 of every sub-chain, then the slabs [n_slices][n_lags + 2][dim] of float64 partial sums
   void* run_ws = nullptr; size_t run_ws_cap = 0;  // mfm_mala_run on the Cox process: the step keys and the per-step info its tallies read
+  void* meads_ws = nullptr; size_t meads_ws_cap = 0;      // mfm_meads_warmup: the folds' parameters and statistics, the staged Y / Z tiles, the Gram partials (ghmc.hip: MeadsBufs)
   void* chees_ws = nullptr; size_t chees_ws_cap = 0;      // mfm_chees_warmup: the CheesState, the column means, g, and the per-chain records the caller did not pass (chees.hip: CheesBufs)
   double* pt_ws = nullptr;                                // mfm_pt_run / mfm_pt_exchange: the ladder, betas then step sizes (pt.hip: PtVec)
   void* svgd_ws = nullptr; size_t svgd_ws_cap = 0;        // mfm_svgd_*: column means, centred coordinates, row norms, selection state (svgd.hip: Scratch)
@@ -409,7 +411,7 @@ extern "C" int mfm_destroy(mfm_ctx* x) { use_ctx(x);
   hipDeviceSynchronize();
   void* ps[] = {x->master, x->mu, x->nu, x->Wp, x->WpT, x->bias, x->fourier, x->acts, x->dzs, x->dacts, x->slabs, x->loss_part, x->eval_pad, x->wsk_partials, x->wsk_tickets, x->wsk_const, x->wsk_wg,
                 x->jobs, x->opt, x->opt_alt, x->flag, x->gmm_mode, x->gmm_std, x->gmm_logw, x->counts, x->Kinv, x->kbias, x->kdiag, x->beta_out,
-                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws, x->pt_ws, x->lgcp_chol};
+                x->d_att, x->att_buf, x->run_ws, x->ac_ws, x->cs_ws, x->d_inv_mass, x->svgd_ws, x->svgd_step_ws, x->chees_ws, x->meads_ws, x->pt_ws, x->lgcp_chol};
   for (void* p : ps) if (p) hipFree(p);
   (void)mfm_comm_destroy(x);
   ode_ws_free(x->ode);
@@ -1021,6 +1023,152 @@ extern "C" int mfm_mclmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1,
   if (launch_mclmc_run(r, x->stream)) return too_large(x, "MCLMC");
   LAUNCHCHK();
   x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+
+// Generalized HMC with persistent momentum (ghmc.hip).  Checks in mfm_hmc_run's order, then the sampler's own: a rejected call touches nothing.
+static int ghmc_check(mfm_ctx* x, double step, double alpha, double delta) {
+  CHECKED(hmc_refuse_cox(x));
+  if (!(step > 0) || std::isinf(step)) return fail(MFM_EINVAL, "step_size must be positive and finite (got %g)", step);
+  if (!(alpha > 0 && alpha <= 1)) return fail(MFM_EINVAL, "alpha must be in (0, 1] (got %g)", alpha);
+  if (!(delta >= 0) || std::isinf(delta)) return fail(MFM_EINVAL, "delta must be finite and not negative (got %g)", delta);
+  return MFM_OK;
+}
+static GhmcArgs ghmc_args(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double alpha, double delta,
+                          const double* d_inverse_mass, float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_slice,
+                          float* d_acc, uint8_t* d_isacc, double* d_de) {
+  GhmcArgs a; memset(&a, 0, sizeof a);
+  a.T = x->net.T; a.key = Key2{k0, k1}; a.keys = d_keys; a.n_total = x->cfg.n_chain_total; a.chain_offset = x->cfg.chain_offset; a.B = x->cfg.n_chain_local;
+  a.beta = beta; a.eps = step; a.alpha = alpha; a.delta = delta;
+  a.pos = d_pos; a.logp = d_logp; a.grad = d_grad; a.mom = d_mom; a.slice = d_slice;
+  a.acc_prob = d_acc; a.accepted = d_isacc; a.energy_change = d_de;
+  a.minv = d_inverse_mass;      // the call's own (non-null: the MASS instances); the context's installed inverse mass is not read
+  return a;
+}
+extern "C" int mfm_ghmc_init(mfm_ctx* x, uint32_t k0, uint32_t k1, const double* d_inverse_mass, double* d_momentum, double* d_slice) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_momentum || !d_slice) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(hmc_refuse_cox(x));
+  ProfScope ps_(x, PROF_MALA);
+  launch_ghmc_init(Key2{k0, k1}, (uint32_t)x->cfg.n_chain_total, (uint32_t)x->cfg.chain_offset, x->cfg.n_chain_local, x->cfg.dim, d_inverse_mass,
+                   d_momentum, d_slice, x->stream);
+  LAUNCHCHK();
+  return MFM_OK;
+}
+static int ghmc_step_common(mfm_ctx* x, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double alpha, double delta,
+                            const double* d_inverse_mass, float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_slice,
+                            float* d_acc, uint8_t* d_isacc, double* d_de) {
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad || !d_mom || !d_slice) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(ghmc_check(x, step, alpha, delta));
+  const GhmcArgs a = ghmc_args(x, k0, k1, d_keys, beta, step, alpha, delta, d_inverse_mass, d_pos, d_logp, d_grad, d_mom, d_slice, d_acc, d_isacc, d_de);
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_ghmc_step(a, x->stream)) return too_large(x, "GHMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += x->cfg.n_chain_local;      // (steps only, as mfm_hmc_step)
+  return MFM_OK;
+}
+extern "C" int mfm_ghmc_step(mfm_ctx* x, uint32_t k0, uint32_t k1, double beta, double step, double alpha, double delta, const double* d_inverse_mass,
+                             float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_slice, float* d_acc, uint8_t* d_isacc,
+                             double* d_de) { use_ctx(x);
+  return ghmc_step_common(x, k0, k1, nullptr, beta, step, alpha, delta, d_inverse_mass, d_pos, d_logp, d_grad, d_mom, d_slice, d_acc, d_isacc, d_de);
+}
+extern "C" int mfm_ghmc_step_keys(mfm_ctx* x, const uint32_t* d_keys, double beta, double step, double alpha, double delta, const double* d_inverse_mass,
+                                  float* d_pos, double* d_logp, float* d_grad, double* d_mom, double* d_slice, float* d_acc, uint8_t* d_isacc,
+                                  double* d_de) { use_ctx(x);
+  if (!d_keys) return fail(MFM_EINVAL, "null key array");
+  return ghmc_step_common(x, 0, 0, d_keys, beta, step, alpha, delta, d_inverse_mass, d_pos, d_logp, d_grad, d_mom, d_slice, d_acc, d_isacc, d_de);
+}
+extern "C" int mfm_ghmc_run(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step, double alpha, double delta,
+                            const double* d_inverse_mass, int32_t n_steps, int32_t thin, float* d_pos, double* d_logp, float* d_grad, double* d_mom,
+                            double* d_slice, int32_t* d_n_acc, double* d_acc_sum, double* d_de_acc_sum, float* d_acc, uint8_t* d_isacc, double* d_de,
+                            float* d_traj_pos, double* d_traj_logp) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad || !d_mom || !d_slice) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_run_keys(key_mode, d_keys, n_steps));
+  CHECKED(check_thin(thin, n_steps, d_traj_pos, d_traj_logp));
+  CHECKED(ghmc_check(x, step, alpha, delta));
+  GhmcRunArgs r; memset(&r, 0, sizeof r);
+  r.m = ghmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step, alpha, delta, d_inverse_mass, d_pos, d_logp, d_grad, d_mom, d_slice,
+                  d_acc, d_isacc, d_de);
+  r.t = RunTail{key_mode, n_steps, thin, d_n_acc, d_acc_sum, d_traj_pos, d_traj_logp};
+  r.de_acc_sum = d_de_acc_sum;
+  ProfScope ps_(x, PROF_MALA);
+  if (launch_ghmc_run(r, x->stream)) return too_large(x, "GHMC");
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)x->cfg.n_chain_local * n_steps;      // (steps only, as mfm_hmc_run)
+  return MFM_OK;
+}
+
+static size_t chees_align(size_t n);      // (defined with the ChEES warmup below: 256-byte sections of a workspace)
+// MEADS warmup of GHMC (ghmc.hip): per iteration four statistics launches, the step and the acceptance mean, enqueued back to back; the
+// host reads nothing until the end
+extern "C" int mfm_meads_plan(int32_t n_valid, int32_t n_folds, int32_t dim, int32_t* h_out) {
+  if (!h_out) return fail(MFM_EINVAL, "null output pointer");
+  if (n_folds < 2) return fail(MFM_EINVAL, "n_folds must be at least 2 (got %d)", n_folds);
+  if (n_valid < 2 * n_folds || n_valid % n_folds) return fail(MFM_EINVAL, "n_valid (%d) must be a multiple of n_folds (%d) with at least 2 chains per fold", n_valid, n_folds);
+  if (dim < 1) return fail(MFM_EINVAL, "dim must be positive (got %d)", dim);
+  const MeadsPlan p = meads_plan(n_valid, n_folds, dim);
+  h_out[0] = p.m; h_out[1] = p.m_pad; h_out[2] = p.d_pad; h_out[3] = p.gram_workgroups;
+  return MFM_OK;
+}
+extern "C" int mfm_meads_warmup(mfm_ctx* x, int key_mode, uint32_t k0, uint32_t k1, const uint32_t* d_keys, double beta, double step0, double alpha0,
+                                int32_t n_iter, int32_t n_valid, int32_t n_folds, int32_t shuffle_every, const int32_t* d_perms, float* d_pos,
+                                double* d_logp, float* d_grad, double* d_mom, double* d_slice, double* h_result, double* d_inverse_mass_out,
+                                double* d_trace, double* d_mass_trace) { use_ctx(x);
+  NEED_TARGET();
+  if (!d_pos || !d_logp || !d_grad || !d_mom || !d_slice) return fail(MFM_EINVAL, "null device pointer");
+  CHECKED(check_run_keys(key_mode, d_keys, n_iter));
+  CHECKED(ghmc_check(x, step0, alpha0, 0.0));
+  const int B = x->cfg.n_chain_local, d = x->cfg.dim, K = n_folds;
+  if (x->cfg.n_chain_total != B)
+    return fail(MFM_EUNSUPPORTED, "the MEADS warmup serves one rank (n_chain_total %d != n_chain_local %d): the fold statistics would need an all-reduce", x->cfg.n_chain_total, B);
+  if (K < 2) return fail(MFM_EINVAL, "n_folds must be at least 2 (got %d)", K);
+  if (n_valid < 2 * K || n_valid % K || n_valid > B)
+    return fail(MFM_EINVAL, "n_valid (%d) must be a multiple of n_folds (%d) with at least 2 chains per fold and at most n_chain_local = %d", n_valid, K, B);
+  if (shuffle_every < 0) return fail(MFM_EINVAL, "shuffle_every must not be negative (got %d)", shuffle_every);
+  const int n_shuffles = shuffle_every > 0 ? (n_iter - 1) / shuffle_every : 0;
+  if (n_shuffles > 0 && !d_perms) return fail(MFM_EINVAL, "shuffle_every > 0 needs d_perms (int32 [(n_iter - 1) / shuffle_every][n_valid], one permutation per shuffle)");
+  if ((d + 63) / 64 > 32) return too_large(x, "GHMC");
+  const MeadsPlan p = meads_plan(n_valid, K, d), pall = meads_plan(n_valid, 1, d);      // (pall: the closing pass, one fold of all chains)
+  // workspace: par [K][8 + d] | fold_of [B] | mu, sd [K][d] | norms [2][K][m_pad] | part | acc [B] | result [4] | yz [2][K][m_pad][d_pad]
+  const size_t n_part = 2 * (size_t)std::max(K * p.n_tiles, pall.n_tiles);
+  const size_t o_fold = chees_align(8 * (size_t)K * (MEADS_PAR + d)), o_mu = o_fold + chees_align(4 * (size_t)B), o_sd = o_mu + chees_align(8 * (size_t)K * d),
+               o_norm = o_sd + chees_align(8 * (size_t)K * d), o_part = o_norm + chees_align(16 * (size_t)K * p.m_pad), o_acc = o_part + chees_align(8 * n_part),
+               o_res = o_acc + chees_align(8 * (size_t)B), o_yz = o_res + chees_align(32),
+               need = o_yz + chees_align(8 * (size_t)K * p.m_pad * p.d_pad);
+  if (x->meads_ws_cap < need) {
+    if (x->meads_ws) { HIPCHK(hipStreamSynchronize(x->stream)); (void)hipFree(x->meads_ws); x->meads_ws = nullptr; x->meads_ws_cap = 0; }
+    HIPCHK(hipMalloc(&x->meads_ws, need));
+    x->meads_ws_cap = need;
+  }
+  char* ws = (char*)x->meads_ws;
+  HIPCHK(hipMemsetAsync(ws + o_fold, 0, 4 * (size_t)B, x->stream));      // (a d_perms that is no permutation leaves entries unwritten: fold 0)
+  MeadsBufs b;
+  b.par = (double*)ws; b.fold_of = (int32_t*)(ws + o_fold); b.mu = (double*)(ws + o_mu); b.sd = (double*)(ws + o_sd); b.norms = (double*)(ws + o_norm);
+  b.part = (double*)(ws + o_part); b.acc = (double*)(ws + o_acc); b.result = (double*)(ws + o_res); b.yz = (float*)(ws + o_yz);
+  const GhmcArgs a = ghmc_args(x, k0, k1, key_mode == 1 ? d_keys : nullptr, beta, step0, alpha0, 0.0, nullptr, d_pos, d_logp, d_grad, d_mom, d_slice,
+                               nullptr, nullptr, nullptr);
+  ProfScope ps_(x, PROF_MALA);
+  hipLaunchKernelGGL(meads_begin_kernel, dim3(std::min(64, (K * (MEADS_PAR + d) + 255) / 256)), dim3(256), 0, x->stream, b.par, K, d, step0, alpha0);
+  const int32_t* perm = nullptr;
+  for (int t = 1; t <= n_iter; ++t) {
+    const int r = shuffle_every > 0 ? (t - 1) / shuffle_every : 0;      // the membership in force: identity, then d_perms[r - 1]
+    const int32_t* pt = r == 0 ? nullptr : d_perms + (size_t)(r - 1) * n_valid;
+    if (t == 1 || pt != perm) hipLaunchKernelGGL(meads_fold_kernel, dim3((B + 255) / 256), dim3(256), 0, x->stream, pt, n_valid, p.m, B, b.fold_of);
+    perm = pt;
+    double* trace_t = d_trace ? d_trace + (size_t)(t - 1) * K * 6 : nullptr;
+    launch_meads_stats(b, d_pos, d_grad, perm, n_valid, K, d, t, 0, nullptr, trace_t, d_mass_trace ? d_mass_trace + (size_t)(t - 1) * K * d : nullptr, x->stream);
+    if (launch_meads_step(a, b, K, key_mode, n_iter, t, x->stream)) return too_large(x, "GHMC");
+    if (trace_t) hipLaunchKernelGGL(meads_accmean_kernel, dim3(1), dim3(256), 0, x->stream, b.acc, perm, n_valid, K, p.m, trace_t);
+  }
+  launch_meads_stats(b, d_pos, d_grad, nullptr, n_valid, 1, d, n_iter + 1, 1, d_inverse_mass_out, nullptr, nullptr, x->stream);
+  LAUNCHCHK();
+  x->ctr[CTR_MALA] += (int64_t)B * n_iter;      // (steps only, as mfm_hmc_run)
+  if (h_result) {                                // the call's only read-back, after everything is enqueued: eps, alpha, delta
+    HIPCHK(hipMemcpyAsync(h_result, b.result, 3 * sizeof(double), hipMemcpyDeviceToHost, x->stream));
+    HIPCHK(hipStreamSynchronize(x->stream));
+  }
   return MFM_OK;
 }
 

@@ -247,6 +247,23 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
         eng.mclmc_energy_count += int(eng.n_valid)
         info["acc"].fill_(1); info["isacc"].fill_(1)
 
+    use_ghmc = getattr(args, "mcmc_kernel", "mala") == "ghmc"
+    if use_ghmc:
+        info["ghmc_de"] = t.empty(n, device=eng.dev, dtype=t.float64)
+        eng.ghmc_momentum = eng.ghmc_slice = None      # [n, d] / [n] float64, drawn at the first GHMC transition and kept by the engine
+
+    def ghmc_train_step(rng_key, beta, pos, logp, grad):
+        """Build-side mode (--mcmc_kernel ghmc): one GHMC transition (mfm_ghmc_step) at --step_size / --ghmc_alpha / --ghmc_delta and the
+        inverse mass the MEADS warmup left (args.ghmc_inverse_mass; None: unit metric).  The engine keeps p and s; a flow move between
+        two transitions replaces x only, which is valid: the stationary law is p(x) N(p; 0, M) uniform(s)."""
+        minv = getattr(args, "ghmc_inverse_mass", None)
+        if eng.ghmc_momentum is None:
+            eng.ghmc_momentum = t.empty(pos.shape, device=eng.dev, dtype=t.float64)
+            eng.ghmc_slice = t.empty(pos.shape[0], device=eng.dev, dtype=t.float64)
+            eng.ctx.ghmc_init(jr.split(rng_key)[1], eng.ghmc_momentum, eng.ghmc_slice, minv)
+        eng.ctx.ghmc_step(rng_key, beta, args.step_size, ghmc_alpha(args), ghmc_delta(args), pos, logp, grad, eng.ghmc_momentum, eng.ghmc_slice, minv,
+                          info["acc"], info["isacc"], info["ghmc_de"])
+
     def train_data_generator(rng_key, states, count, vector_field_param=None, beta=1.0):
         """:300-314.  States are updated IN PLACE (and returned); infos are views of reused device buffers."""
         _maybe_upload(eng, vector_field_param)
@@ -267,6 +284,8 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
             info["acc"].copy_(info["nuts_acc"]); info["isacc"].fill_(1)
         elif use_mclmc:
             mclmc_train_step(rng_key, beta, pos, logp, grad)
+        elif use_ghmc:
+            ghmc_train_step(rng_key, beta, pos, logp, grad)
         else:
             eng.ctx.mala_step(rng_key, beta, args.step_size, pos, logp, grad, info["acc"], info["isacc"], info["prop"], info["w"])
         return MALAState(pos, logp, grad), MALAInfo(info["acc"], info["isacc"], info["prop"], info["w"])
@@ -282,7 +301,7 @@ def create_train_data_gn(dist, vector_field_apply, ode_integrator, args):
     train_data_generator.info_buffers = info
     # what run() needs to issue generator + train_step as ONE library call (mfm_train_iter) where that is the same computation
     train_data_generator.flow_mode = mode
-    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc and not use_nuts and not use_mclmc
+    train_data_generator.one_call_ok = n_is <= 0 and args.mcmc_per_flow_steps >= 1 and float(args.mcmc_per_flow_steps).is_integer() and not use_hmc and not use_nuts and not use_mclmc and not use_ghmc
     return train_data_generator, init_fn, transform_and_logdet
 
 
@@ -349,6 +368,7 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     check_adapt_args(args)                                                                  # --adapt_steps (build-side addition)
     check_cox_args(dist, args)                                                              # --example pines: what its HMC kernel does not serve
     check_mclmc_args(args)                                                                  # --mcmc_kernel mclmc: --mclmc_L, --mclmc_integrator
+    check_ghmc_args(dist, args)                                                             # --mcmc_kernel ghmc: --ghmc_alpha, --ghmc_delta, --meads_folds, --meads_shuffle
     learning_iter = args.learning_iter
     iter_per_temp = args.anneal_iter // args.num_anneal_temp                                # :330
     n_iter, n_chain = args.eval_iter, args.num_chain
@@ -395,6 +415,12 @@ def run(dist, args, target_gn=None, log_every=1, return_extras=False):
     adapt_stats = adapt_step_size(eng, dist, args, pos0, key_gen)                           # --adapt_steps ({} at 0): sets args.step_size
     if "adapted_L" in adapt_stats:                                                          # (--mcmc_kernel mclmc)
         logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']}, L= {adapt_stats['adapted_L']} (energy variance per dimension= {adapt_stats['adapt_energy_var']})")
+        wandb.log(adapt_stats)
+        train_start += time.time() - adapt_start
+    elif "adapted_alpha" in adapt_stats:                                                    # (--mcmc_kernel ghmc: the MEADS warmup)
+        logger.info(f"Adapted step size= {adapt_stats['adapted_step_size']}, alpha= {adapt_stats['adapted_alpha']}, inverse mass in "
+                    f"[{adapt_stats['adapted_inverse_mass_min']:.4g}, {adapt_stats['adapted_inverse_mass_max']:.4g}] "
+                    f"(mean acceptance rate of the last warmup iteration= {adapt_stats['adapt_acceptance']})")
         wandb.log(adapt_stats)
         train_start += time.time() - adapt_start
     elif adapt_stats:
@@ -545,7 +571,7 @@ def check_adapt_args(args):
     kern = getattr(args, "mcmc_kernel", "mala")
     if kern == "mclmc" and getattr(args, "adapt_mass", False):
         raise ValueError("--adapt_mass is not served with --mcmc_kernel mclmc: the MCLMC kernel (mfm_mclmc_*) runs at unit metric")
-    if n_steps > 0 and kern not in ("hmc", "nuts", "mclmc"):
+    if n_steps > 0 and kern not in ("hmc", "nuts", "mclmc", "ghmc"):
         raise ValueError("--adapt_steps needs --mcmc_kernel hmc: the training loop's MALA step uses the acceptance rule AS WRITTEN, which accepts "
                          "with min(1, 1 / alpha); its acceptance does not fall as the step grows, so dual averaging has nothing to steer by")
     hmc_adapt = getattr(args, "hmc_adapt", "dual")
@@ -576,6 +602,8 @@ def check_cox_args(dist, args):
         raise ValueError("--do_pt is not served with --example pines: parallel tempering (mfm_pt_run) has no local move for the Cox process")
     if kern == "mclmc":
         raise ValueError("--mcmc_kernel mclmc is not served with --example pines: MCLMC (mfm_mclmc_*) has no Cox process kernel (use --mcmc_kernel hmc)")
+    if kern == "ghmc":
+        raise ValueError("--mcmc_kernel ghmc is not served with --example pines: GHMC (mfm_ghmc_*) has no Cox process kernel (use --mcmc_kernel hmc)")
     if kern == "nuts":
         raise ValueError("--mcmc_kernel nuts is not served with --example pines: the No-U-turn sampler has no Cox process kernel (use --mcmc_kernel hmc)")
     if getattr(args, "adapt_mass", False):
@@ -595,6 +623,44 @@ def check_mclmc_args(args):
         raise ValueError(f"--mclmc_L must be positive, or 0 for sqrt(dim) (got {args.mclmc_L})")
     from .bblackjax.mcmc.mclmc import integrator_id
     integrator_id(getattr(args, "mclmc_integrator", "mclachlan"))
+
+
+def check_ghmc_args(dist, args):
+    """``--mcmc_kernel ghmc``'s own flags and what does not go with it, before any device work."""
+    if getattr(args, "mcmc_kernel", "mala") != "ghmc":
+        return
+    from .bblackjax.adaptation.meads_adaptation import check_folds
+    from .bblackjax.mcmc.ghmc import check_parameters
+    if getattr(dist, "kind", None) == "lgcp":
+        raise ValueError("--mcmc_kernel ghmc is not served with --example pines: GHMC (mfm_ghmc_*) has no Cox process kernel (use --mcmc_kernel hmc)")
+    if getattr(args, "adapt_mass", False):
+        raise ValueError("--adapt_mass is not served with --mcmc_kernel ghmc: its --adapt_steps warmup is MEADS, which sets the mass itself")
+    if getattr(args, "hmc_adapt", "dual") == "chees":
+        raise ValueError("--hmc_adapt chees is not served with --mcmc_kernel ghmc: a GHMC transition has no trajectory length to adapt")
+    if getattr(args, "nuts_adapt", "hmc") == "tree":
+        raise ValueError("--nuts_adapt tree is not served with --mcmc_kernel ghmc: it adapts on the No-U-turn sampler's trees")
+    if getattr(args, "do_pt", False):
+        raise ValueError("--do_pt is not served with --mcmc_kernel ghmc: parallel tempering takes mala or hmc as its local move")
+    check_parameters(args.step_size, getattr(args, "ghmc_alpha", 0.5), getattr(args, "ghmc_delta", None))
+    if int(getattr(args, "meads_shuffle", 0) or 0) < 0:
+        raise ValueError(f"--meads_shuffle must not be negative (got {args.meads_shuffle})")
+    if int(getattr(args, "adapt_steps", 0) or 0) > 0:
+        try:
+            check_folds(int(args.num_chain), int(getattr(args, "meads_folds", 4)))
+        except ValueError as e:
+            raise ValueError(f"--mcmc_kernel ghmc --adapt_steps: num_chain ({args.num_chain}) must be a multiple of --meads_folds "
+                             f"({getattr(args, 'meads_folds', 4)} >= 2) with at least 2 chains per fold") from e
+
+
+def ghmc_delta(args):
+    """``--ghmc_delta``: the slice drift of ``--mcmc_kernel ghmc``; not given: ``--ghmc_alpha / 2``."""
+    delta = getattr(args, "ghmc_delta", None)
+    return ghmc_alpha(args) / 2.0 if delta is None else float(delta)
+
+
+def ghmc_alpha(args):
+    """``--ghmc_alpha``: the momentum refresh rate of ``--mcmc_kernel ghmc`` (default 0.5)."""
+    return float(getattr(args, "ghmc_alpha", 0.5))
 
 
 def mclmc_L(args):
@@ -656,6 +722,19 @@ def adapt_step_size(eng, dist, args, pos0, key_gen):
         # adapt_energy_var: the variance per dimension of the LAST step-size round, the one the returned step size was derived from (at the
         # phase-2 L; the phase-3 run that follows only replaces L)
         return dict(adapted_step_size=params.step_size, adapted_L=params.L, adapt_energy_var=[h for h in history if h[0] != 3][-1][3])
+    if getattr(args, "mcmc_kernel", "mala") == "ghmc":
+        # --mcmc_kernel ghmc: N MEADS iterations (meads_adaptation, mfm_meads_warmup) on the copy at beta = 1, from --step_size / --ghmc_alpha;
+        # args.step_size, args.ghmc_alpha, args.ghmc_delta and args.ghmc_inverse_mass (a float64 device vector) are set
+        from .bblackjax.adaptation.meads_adaptation import meads_adaptation
+        if eng.world > 1:
+            raise ValueError("--mcmc_kernel ghmc --adapt_steps serves one rank: the MEADS fold statistics would need an all-reduce")
+        warm = meads_adaptation(dist.logprob, eng.n_valid, int(getattr(args, "meads_folds", 4)), int(getattr(args, "meads_shuffle", 0) or 0),
+                                args.step_size, ghmc_alpha(args))
+        (_, par), minfo = warm.run(jr.split(key_gen, 4)[3], pos0.clone(), n_steps)
+        minv = par["momentum_inverse_scale"] ** 2
+        args.step_size, args.ghmc_alpha, args.ghmc_delta, args.ghmc_inverse_mass = par["step_size"], par["alpha"], par["delta"], minv.contiguous()
+        return dict(adapted_step_size=par["step_size"], adapted_alpha=par["alpha"], adapted_inverse_mass_min=minv.min().item(),
+                    adapted_inverse_mass_max=minv.max().item(), adapt_acceptance=minfo.mean_acceptance[-1].mean().item())
     from .bblackjax.mcmc.hmc import hmc
     from .engine import global_mean_std
     if getattr(args, "hmc_adapt", "dual") == "chees":
@@ -733,6 +812,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     use_hmc = getattr(args, "mcmc_kernel", "mala") == "hmc"
     use_nuts = getattr(args, "mcmc_kernel", "mala") == "nuts"
     use_mclmc = getattr(args, "mcmc_kernel", "mala") == "mclmc"
+    use_ghmc = getattr(args, "mcmc_kernel", "mala") == "ghmc"
     # the kernel, the state it starts from, its key and what a step costs in gradient evaluations ...
     key, run_kw = jr.split(key_gen, 3)[2], {}
     if use_mclmc:          # fresh unit momenta from one half of the key, the run on the other; 1 (leapfrog) or 2 (McLachlan) gradients per step
@@ -741,6 +821,12 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
         algo = mclmc(dist.logprob, mclmc_L(args), args.step_size, integ)
         k_init, key = jr.split(key)
         start, grads_per_step = algo.init(states.position, k_init), float(integ + 1)
+    elif use_ghmc:         # fresh momenta and slice variables from one half of the key, the run on the other; ONE gradient per transition
+        from .bblackjax.mcmc.ghmc import ghmc
+        minv = getattr(args, "ghmc_inverse_mass", None)
+        algo = ghmc(dist.logprob, args.step_size, ghmc_alpha(args), ghmc_delta(args), None if minv is None else minv.sqrt())
+        k_init, key = jr.split(key)
+        start, grads_per_step = algo.init(states.position, k_init), 1.0
     elif use_hmc:
         from .bblackjax.mcmc.hmc import hmc
         algo = hmc(dist.logprob, args.step_size, int(args.hmc_steps), getattr(args, "inverse_mass_matrix", None))      # (--adapt_mass)
@@ -773,7 +859,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
         means = [global_mean_std(per_chain[:, q].contiguous(), eng.n_total)[0].item() for q in range(3)]
         grads_per_step = means[0]
         out.update(nuts_mean_leapfrog=means[0], nuts_mean_depth=means[1], nuts_divergent=int(round(means[2] * eng.n_total)))
-    if use_hmc or use_nuts or use_mclmc:
+    if use_hmc or use_nuts or use_mclmc or use_ghmc:
         for name in ("min", "median", "mean"):
             out["ess_per_grad_" + name] = out["ess_per_step_" + name] / grads_per_step
     # across the chains (of all ranks): split-R-hat and the multi-chain ESS, per step and chain (diagnostics.py; a chain stuck in one
@@ -783,7 +869,7 @@ def chain_ess_per_step(eng, dist, args, states, key_gen):
     rhat, multi = cd.rhat.double(), cd.ess.double() / (float(eng.n_total) * n_steps)
     out.update(rhat_max=rhat.max().item(), rhat_median=rhat.median().item(), ess_multichain_per_step_min=multi.min().item(),
                ess_multichain_per_step_median=multi.median().item(), ess_multichain_per_step_mean=multi.mean().item())
-    if use_hmc or use_nuts or use_mclmc:
+    if use_hmc or use_nuts or use_mclmc or use_ghmc:
         for name in ("min", "median", "mean"):
             out["ess_multichain_per_grad_" + name] = out["ess_multichain_per_step_" + name] / grads_per_step
     return out

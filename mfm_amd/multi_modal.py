@@ -7,6 +7,7 @@ values ``main`` hard-codes per example (needed for BASELINE.json's phi-four d=25
 ``--adapt_steps N --adapt_target p`` (with ``--mcmc_kernel hmc``) replaces ``--step_size`` by the result of N dual-averaging warmup steps before training (``--adapt_mass``: those steps also adapt a diagonal mass matrix, in windows; ``--mcmc_kernel nuts --nuts_adapt tree``: the warmup is the No-U-turn sampler's own, on its trees' acceptance statistic; ``--hmc_adapt chees``: the N steps are ChEES-HMC iterations, which adapt the step size and the trajectory length across the chains, and the HMC steps then make a jittered number of leapfrog steps in place of ``--hmc_steps``),
 with ``--example pines`` ``--mcmc_kernel hmc``, the ``--hmc_adapt dual`` warmup and ``--ess_steps`` run on the Cox process's own HMC kernel (``mfm_cox_hmc_*``, dim <= 1024: ``--force_dim``); ``--adapt_mass``, ``--hmc_adapt chees``, ``--mcmc_kernel nuts`` and ``--do_pt`` are refused there,
 ``--mcmc_kernel mclmc --mclmc_L L --mclmc_integrator leapfrog|mclachlan`` takes an unadjusted microcanonical Langevin step (no accept test; ``L`` 0: ``sqrt(dim)``) per non-flow iteration and logs ``energy_var_per_dim``; with it ``--adapt_steps N`` tunes the step size and ``L`` (``mclmc_find_L_and_step_size``: ``adapted_step_size``, ``adapted_L``, ``adapt_energy_var``) and ``--ess_steps`` also divides by the 1 or 2 gradients of a step; ``--example pines``, ``--adapt_mass``, ``--hmc_adapt chees`` and ``--do_pt`` are refused with it,
+``--mcmc_kernel ghmc --ghmc_alpha A --ghmc_delta D`` takes one generalized-HMC transition (one leapfrog step, persistent momentum, slice accept; ``D`` not given: ``A / 2``) per non-flow iteration; with it ``--adapt_steps N --meads_folds K --meads_shuffle S`` runs the MEADS warmup (``meads_adaptation``: ``adapted_step_size``, ``adapted_alpha``, ``adapted_inverse_mass_min`` / ``_max``, ``adapt_acceptance``) and ``--ess_steps`` logs ``ess_per_grad_*`` equal to ``ess_per_step_*``; ``--example pines``, ``--adapt_mass``, ``--hmc_adapt chees``, ``--nuts_adapt tree`` and ``--do_pt`` are refused with it,
 ``--ode_method rk4|euler --ode_steps N`` integrates the flow on N equal steps instead of the reference's adaptive Dopri5.
 ``--do_smc`` runs the tempered-SMC baseline on the same MALA kernel (``exe_others.py:79-111``); ``--do_svgd`` (with ``--svgd_optimizer sgd|adagrad|adam|cocob --svgd_step_size``) runs Stein variational gradient descent on the initial particles (``bblackjax/vi/svgd.py``, one rank); ``--do_eslice`` (``--example pines``) runs elliptical slice sampling on the Cox process (``bblackjax/mcmc/elliptical_slice.py``, one rank); the other baselines
 (``--do_flowmc`` ... ``--do_fab``) wrap third-party samplers outside the hot-path scope and raise.
@@ -168,7 +169,7 @@ def build_parser():
     parser.add_argument('--ode_steps', type=int, default=0)
     # the MCMC move of a non-flow iteration: the reference's MALA step (exe_flow_matching.py:313), or -- BASELINE.json's "MALA/HMC" step,
     # not in the reference -- an HMC step of --hmc_steps velocity-Verlet steps of size --step_size (mfm_amd/bblackjax/mcmc/hmc.py)
-    parser.add_argument('--mcmc_kernel', type=str, default='mala', choices=['mala', 'hmc', 'nuts', 'mclmc'])
+    parser.add_argument('--mcmc_kernel', type=str, default='mala', choices=['mala', 'hmc', 'nuts', 'mclmc', 'ghmc'])
     parser.add_argument('--hmc_steps', type=int, default=10)
     # 'nuts': a No-U-turn transition of step size --step_size whose tree doubles at most --max_tree_depth times (mfm_amd/bblackjax/mcmc/nuts.py)
     parser.add_argument('--max_tree_depth', type=int, default=10)
@@ -177,6 +178,14 @@ def build_parser():
     # tunes step size and L (mclmc_find_L_and_step_size); not with --example pines, --adapt_mass, --hmc_adapt chees or --do_pt
     parser.add_argument('--mclmc_L', type=float, default=0.0)
     parser.add_argument('--mclmc_integrator', type=str, default='mclachlan', choices=['leapfrog', 'mclachlan'])
+    # 'ghmc': a generalized-HMC transition (mfm_amd/bblackjax/mcmc/ghmc.py): ONE leapfrog step of size --step_size, the momentum refreshed
+    # at rate --ghmc_alpha in (0, 1] and kept across transitions, a slice accept drifting by --ghmc_delta (not given: alpha / 2).
+    # --adapt_steps N runs the MEADS warmup (meads_adaptation) over --meads_folds folds of the chains, redrawn every --meads_shuffle
+    # iterations (0: never); not with --example pines, --adapt_mass, --hmc_adapt chees, --nuts_adapt tree or --do_pt
+    parser.add_argument('--ghmc_alpha', type=float, default=0.5)
+    parser.add_argument('--ghmc_delta', type=float, default=None)
+    parser.add_argument('--meads_folds', type=int, default=4)
+    parser.add_argument('--meads_shuffle', type=int, default=0)
     # the phi-four lattice's boundary (distributions.py:114-139; the reference's main script builds Dirichlet 0): both ends held at
     # --phi4_bc_value, or a periodic ring (--phi4_bc pbc; the value is ignored)
     parser.add_argument('--phi4_bc', type=str, default='dirichlet', choices=['dirichlet', 'pbc'])
