@@ -11,8 +11,17 @@ unstable   64   16   16       2   0  4       fold 0 starts with all chains at ON
 gmm4_k2    2    16   16       2   0  24      the mixture path, d = 2 (d_pad = 32); the only case whose iterations outlast the floor
                                              1 / (t eps) of gamma, so that 1 / sqrt(lam(Y)) sets alpha
 
-phi-four on the chain (Dirichlet 0) from tests/ghmc_cases.py's start states after a short walk (``start_state``); ``step0`` / ``alpha0``
-are 0.01 / 0.5 except where stated.
+d320_k4    320  32   32       4   0  3       MAXIT 16: the out-of-line trajectory; d_pad = 320, a Gram K-loop of 10 chunks, 5 column blocks
+d1100_k4   1100 32   32       4   0  3       MAXIT 32; d_pad = 1120; the closing pass's inverse mass beyond d = 1024
+d65_pbc_k4 65   32   32       4   0  3       the run-time boundary (BCRT) at MAXIT 4: the step kernel's own halo cells wrap around
+32x32_k4   1024 32   32       4   0  3       BCRT at MAXIT 16, its last dimension: a lattice inside a frame held at 0.5
+k6         64   48   48       6   0  3       six folds of m = 8: waves 0 and 1 of the update kernel own two folds each (f and f + 4), and the roll
+                                             carries fold 3's statistics (wave 3) to fold 4 (wave 0's second) and fold 5's (wave 1) to fold 0
+d64_pbc_k4 64   32   32       4   0  3       BCRT at MAXIT 1
+d1025_pbc_k4 1025 32 32       4   0  4     BCRT at MAXIT 32: the last lane group holds one element, whose right neighbour is element 0
+
+phi-four from tests/ghmc_cases.py's start states after a short walk (``start_state``); ``step0`` / ``alpha0`` are 0.01 / 0.5 except where
+stated (d320_k4: 0.005, d1100_k4 and d1025_pbc_k4: 0.002 -- below the targets' stability limits, so that the first iteration moves chains).
 
 ``reference(case)``: the restatement's own warmup in the device's number formats (tests/meads_ref.py with ``float32_positions=True`` and
 the float32 gradient).  ``TOLERANCE[case]`` = (lam(Z), lam(Y), dH): for the two eigenvalue estimates the RELATIVE tolerance, 4 x the
@@ -45,6 +54,19 @@ CASES = {
     "unstable": ("d64_d0", 16, 16, 2, 0, 4, 1.0, 0.5),
     "gmm4_k2": ("gmm4", 16, 16, 2, 0, 24, 0.5, 0.5),
 }
+NEW_CASES = {
+    "d320_k4": ("d320_d0", 32, 32, 4, 0, 3, 0.005, 0.5),
+    "d1100_k4": ("d1100_d0", 32, 32, 4, 0, 3, 0.002, 0.5),
+    "d65_pbc_k4": ("d65_pbc", 32, 32, 4, 0, 3, 0.01, 0.5),
+    "32x32_k4": ("32x32_db", 32, 32, 4, 0, 3, 0.01, 0.5),
+    "k6": ("d64_d0", 48, 48, 6, 0, 3, 0.01, 0.5),
+    "d64_pbc_k4": ("d64_pbc", 32, 32, 4, 0, 3, 0.01, 0.5),
+    # (4 iterations: over 3 a chain's | log|s| + dH | is 7 x the dH tolerance, short of the 10 x the comparison of decisions needs)
+    "d1025_pbc_k4": ("d1025_pbc", 32, 32, 4, 0, 4, 0.002, 0.5),
+}
+# the seeds count along this order: the first seven cases by name, then the later ones in the order they were added
+SEED_ORDER = sorted(CASES) + list(NEW_CASES)
+CASES.update(NEW_CASES)
 # (case, iteration, receiving fold) whose parameters are KEPT on purpose
 KEPT = {("unstable", 1, 1)}
 
@@ -57,6 +79,14 @@ TOLERANCE = {
     "m80": (8.1e-05, 1.9e-05, 3.2e-05),
     "unstable": (8.6e-05, 8.1e-05, 1.9e-05),
     "gmm4_k2": (3.8e-06, 3.1e-06, 9.1e-06),
+    # the float32 dot-product bound (d + 8) 2^-23 per Gram entry is 3.9e-5 at d = 320 and 1.3e-4 at d = 1100, against 8.7e-6 at d = 65
+    "d320_k4": (0.00091, 8.3e-05, 9.4e-05),
+    "d1100_k4": (0.0052, 0.00028, 0.00047),
+    "d65_pbc_k4": (0.00012, 1.8e-05, 4.9e-05),
+    "32x32_k4": (0.0052, 0.0017, 0.00016),
+    "k6": (0.00011, 2e-05, 2.7e-05),
+    "d64_pbc_k4": (0.00011, 1.8e-05, 3.9e-05),
+    "d1025_pbc_k4": (0.0066, 0.00025, 0.00063),
 }
 
 
@@ -74,18 +104,19 @@ def shape(case):
 
 
 def run_key(case):
-    return prng.PRNGKey(7200 + sorted(CASES).index(case))
+    return prng.PRNGKey(7200 + SEED_ORDER.index(case))
 
 
 def shuffle_key(case):
-    return prng.PRNGKey(7300 + sorted(CASES).index(case))
+    return prng.PRNGKey(7300 + SEED_ORDER.index(case))
 
 
 def init_key(case):
-    return prng.PRNGKey(7400 + sorted(CASES).index(case))
+    return prng.PRNGKey(7400 + SEED_ORDER.index(case))
 
 
-THERMALISE = (60, 0.02, 0.3)                          # transitions, step size, alpha of the walk that spreads the start states
+# transitions, step size, alpha of the walk that spreads the start states; the step size is the target case's own where that is smaller
+THERMALISE = (60, 0.02, 0.3)
 
 
 @functools.lru_cache(maxsize=None)
@@ -96,10 +127,11 @@ def start_state(case):
     tc, B = target(case), CASES[case][1]
     base = gc.start_state(tc)
     x = np.concatenate([base] * -(-B // base.shape[0]))[:B].astype(np.float64)
-    seed = 7500 + sorted(CASES).index(case)
+    seed = 7500 + SEED_ORDER.index(case)
     if tc != "gmm4":
         vg = gc.value_and_grad(tc)
         n, eps, alpha = THERMALISE
+        eps = min(eps, gc.STEP_SIZES[tc][False])
         st, _ = ghmc_ref.run(prng.PRNGKey(seed), ghmc_ref.init(x, vg, prng.PRNGKey(seed + 50), None, B), vg, eps, alpha, alpha / 2, n)
         x = st.position
     if case == "unstable":

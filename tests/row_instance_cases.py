@@ -14,10 +14,15 @@ of the layer as much; each plus (0.5 / d) N(0, 1) noise (oracle.prng draws), rou
 Step sizes (``STEP_SIZES``): chosen with the float64 oracle on a CPU (``scan`` below) so that the case's three steps hold accepted
 and rejected proposals, at most one chain per step lies inside the borderline band the GPU test excludes and none near its edge;
 tests/test_row_instance_cases.py asserts the conditions the GPU test relies on (both decisions; at most 1 of 16 chains per step
-inside the band).  ``HMC_F32_DISTANCE``: what the device's number formats cost the HMC energies against the oracle (see there)."""
+inside the band).  ``HMC_F32_DISTANCE``: what the device's number formats cost the HMC energies against the oracle (see there).
+
+The sampler ``"hmc_mass"`` is the HMC step under the diagonal inverse mass ``hmc_mass_ref.log_spaced_mass(d)`` (tests/hmc_mass_ref.py
+is its float64 restatement), on ``MASS_CASES``: one case per (MAXIT 16 / 32, BCRT false / true) cell and BCRT at MAXIT 4, for
+tests/test_gpu_hmc_mass.py.  ``MASS_STEP_SIZES`` and ``HMC_MASS_F32_DISTANCE`` are its two tables, made and checked as the unit-mass ones."""
 import numpy as np
 
 from oracle import hmc as ohmc, mala as omala, prng, targets
+from tests import hmc_mass_ref
 from tests.mcmc_bits_cases import VARIANTS
 from tests.phi4_2d_oracle import PhiFour2D
 from tests.phi4_bc_oracle import PhiFourBC
@@ -37,6 +42,8 @@ for _L in (17, 32, 33, 45):
         CASES[f"{_L}x{_L}_{_bc}"] = (_L * _L, _L, _bc, N_CHAINS, 0)
 
 SAMPLERS = ("mala", "hmc")
+# MAXIT 16 / 32 x BCRT false / true under a non-unit mass, and BCRT at MAXIT 4 (tests/test_gpu_hmc_mass.py has MAXIT 1 and 4 on Dirichlet 0)
+MASS_CASES = ("d65_pbc", "d257_d0", "17x17_db", "d1025_d0", "d2048_pbc")
 
 # case: {sampler: {variant: step size}} -- written by ``scan`` (run this module), not by hand
 STEP_SIZES = {
@@ -65,6 +72,25 @@ STEP_SIZES = {
     "45x45_pbc": {"mala": {"b1": 0.0018, "b037_textbook": 0.00018}, "hmc": {"b1": 0.0068, "b037_textbook": 0.01}},
     "45x45_db": {"mala": {"b1": 0.0018, "b037_textbook": 0.00015}, "hmc": {"b1": 0.01, "b037_textbook": 0.012}},
 }
+
+
+# case: {variant: step size} of the sampler "hmc_mass" -- written by ``scan`` (run this module with --mass), not by hand
+MASS_STEP_SIZES = {
+    "d65_pbc": {"b1": 0.022, "b037_textbook": 0.038},
+    "d257_d0": {"b1": 0.0056, "b037_textbook": 0.01},
+    "17x17_db": {"b1": 0.015, "b037_textbook": 0.026},
+    "d1025_d0": {"b1": 0.0018, "b037_textbook": 0.0032},
+    "d2048_pbc": {"b1": 0.001, "b037_textbook": 0.0018},
+}
+
+
+def step_size(case, sampler, variant):
+    return MASS_STEP_SIZES[case][variant] if sampler == "hmc_mass" else STEP_SIZES[case][sampler][variant]
+
+
+def inverse_mass(case):
+    """The diagonal inverse mass of the sampler "hmc_mass": log-spaced over [0.25, 4] in a fixed permutation."""
+    return hmc_mass_ref.log_spaced_mass(CASES[case][0])
 
 
 def maxit(d):
@@ -143,6 +169,8 @@ def oracle_step(sampler, variant, st, vg, keys, eps):
     """One float64 oracle step: (new state, info, u)."""
     if sampler == "hmc":
         return ohmc.kernel(keys, st, vg, eps, HMC_LEAPFROG)
+    if sampler == "hmc_mass":
+        return hmc_mass_ref.kernel(keys, st, vg, eps, HMC_LEAPFROG, hmc_mass_ref.log_spaced_mass(st.position.shape[1]))
     return omala.kernel(keys, st, vg, eps, textbook=VARIANTS[variant][1])
 
 
@@ -164,7 +192,7 @@ def borderline(sampler, st, info, u):
 def oracle_run(case, sampler, variant, eps=None):
     """The oracle alone over the case's three steps, restarting each step from the float32-rounded position as the device's state is:
     per step (decisions, |u - p| in units of the band, max |log pi| of the state the step started from)."""
-    eps = STEP_SIZES[case][sampler][variant] if eps is None else eps
+    eps = step_size(case, sampler, variant) if eps is None else eps
     vg = value_and_grad(case, variant)
     st = omala.init(start_state(case).astype(np.float64), vg)
     out = []
@@ -202,35 +230,38 @@ def grad32(case, x, beta):
     return f(beta) * (-f(TBETA) * (coef * lap - x * (f(1) - x * x) / coef))
 
 
-def hmc_step_f32(case, variant, st, keys, eps):
-    """The oracle's HMC step (oracle/hmc.py) restated with the device's number formats: the position rounded to float32 after every
-    drift, the gradient in float32 arithmetic (``grad32``), momentum, energies and the log-density (of the float32 position) in
-    float64.  Returns (log acceptance probability, end position, its log-density, its gradient)."""
+def hmc_step_f32(case, variant, st, keys, eps, minv=None):
+    """The oracle's HMC step (oracle/hmc.py; with ``minv`` tests/hmc_mass_ref.py's) restated with the device's number formats: the
+    position rounded to float32 after every drift, the gradient in float32 arithmetic (``grad32``), momentum, energies and the
+    log-density (of the float32 position) in float64.  Returns (log acceptance probability, end position, its log-density, its
+    gradient)."""
     beta = VARIANTS[variant][0]
     dist = oracle_dist(case)
     x, lp, g = st.position.astype(np.float32), st.logdensity, st.logdensity_grad.astype(np.float32)
-    p = prng.normal_rows(prng.split_rows(keys, 2)[:, 0], x.shape[1])
-    h0 = -lp + 0.5 * (p * p).sum(1)
+    minv = np.ones(x.shape[1]) if minv is None else minv
+    p = prng.normal_rows(prng.split_rows(keys, 2)[:, 0], x.shape[1]) / np.sqrt(minv)
+    h0 = -lp + 0.5 * (minv * p * p).sum(1)
     for _ in range(HMC_LEAPFROG):
         p = p + 0.5 * eps * g.astype(np.float64)
-        x = (x.astype(np.float64) + eps * p).astype(np.float32)
+        x = (x.astype(np.float64) + eps * (minv * p)).astype(np.float32)
         lp, g = beta * dist.loglik(x.astype(np.float64)), grad32(case, x, beta)
         p = p + 0.5 * eps * g.astype(np.float64)
-    h1 = -lp + 0.5 * (p * p).sum(1)
+    h1 = -lp + 0.5 * (minv * p * p).sum(1)
     return np.minimum(h0 - h1, 0.0), x, lp, g
 
 
-def hmc_f32_distance(case, variant):
+def hmc_f32_distance(case, variant, sampler="hmc"):
     """The float32 restatement against the float64 oracle over the case's three steps (the oracle's own trajectory): the largest
     differences of the log acceptance probability and of the end point's log-density."""
-    eps = STEP_SIZES[case]["hmc"][variant]
+    eps = step_size(case, sampler, variant)
+    minv = inverse_mass(case) if sampler == "hmc_mass" else None
     vg = value_and_grad(case, variant)
     st = omala.init(start_state(case).astype(np.float64), vg)
     d_p = d_lp = 0.0
     for j in range(N_STEPS):
-        keys = step_keys(case, j, "hmc")[1]
-        new, info, u = oracle_step("hmc", variant, st, vg, keys, eps)
-        lpa, x, lp, g = hmc_step_f32(case, variant, st, keys, eps)
+        keys = step_keys(case, j, sampler)[1]
+        new, info, u = oracle_step(sampler, variant, st, vg, keys, eps)
+        lpa, x, lp, g = hmc_step_f32(case, variant, st, keys, eps, minv)
         d_p = max(d_p, np.abs(lpa - np.minimum(info.energy_delta, 0.0)).max())
         d_lp = max(d_lp, np.abs(lp - vg(info.proposed_position)[0]).max())
         st = omala.init(new.position.astype(np.float32).astype(np.float64), vg)
@@ -270,6 +301,18 @@ HMC_F32_DISTANCE = {
 }
 
 
+# case: {variant: (log acceptance probability, end point's log-density)} under ``inverse_mass(case)``: ``hmc_f32_distance(case, variant,
+# "hmc_mass")`` rounded up to two digits.  The mass changes what the formats cost (a drift of eps minv_j p_j rounds a larger step where
+# minv_j = 4), so tests/test_gpu_hmc_mass.py takes 4 x THIS distance, not the unit-mass one.
+HMC_MASS_F32_DISTANCE = {
+    "d65_pbc": {"b1": (1.1e-05, 8.4e-06), "b037_textbook": (7.3e-06, 6.3e-06)},
+    "d257_d0": {"b1": (2.2e-05, 2.1e-05), "b037_textbook": (2.5e-05, 2.1e-05)},
+    "17x17_db": {"b1": (1.4e-05, 1.4e-05), "b037_textbook": (7e-06, 8.7e-06)},
+    "d1025_d0": {"b1": (7.1e-05, 6.2e-05), "b037_textbook": (4.7e-05, 5.1e-05)},
+    "d2048_pbc": {"b1": (0.00017, 0.00021), "b037_textbook": (0.00012, 0.00012)},
+}
+
+
 def scan(case, sampler, variant, grid):
     """Of the step sizes of ``grid`` with at most one chain per step inside the band and none within a quarter of its width of its
     edge: the one with the most even mix of accepted and rejected proposals (at least 2 of each), or None."""
@@ -283,8 +326,23 @@ def scan(case, sampler, variant, grid):
     return best
 
 
-if __name__ == "__main__":                            # prints the STEP_SIZES table
+def _up2(v):
+    """v rounded up to two significant digits."""
+    e = int(np.floor(np.log10(v))) - 1
+    return float(f"{np.ceil(v / 10.0 ** e) * 10.0 ** e:.2g}")
+
+
+if __name__ == "__main__":                            # prints the STEP_SIZES table; with --mass, MASS_STEP_SIZES and HMC_MASS_F32_DISTANCE
     import sys
+    if sys.argv[1:2] == ["--mass"]:
+        grid = [float(f"{10.0 ** (-4 + k / 12):.2g}") for k in range(43)]
+        for case in sys.argv[2:] or MASS_CASES:
+            MASS_STEP_SIZES[case] = {v: scan(case, "hmc_mass", v, grid) for v in VARIANTS}
+            print(f'    "{case}": {MASS_STEP_SIZES[case]},', flush=True)
+        for case in sys.argv[2:] or MASS_CASES:
+            row = {v: tuple(_up2(x) for x in hmc_f32_distance(case, v, "hmc_mass")) for v in VARIANTS}
+            print(f'    "{case}": {row},', flush=True)
+        sys.exit(0)
     grids = {"mala": [float(f"{10.0 ** (-7 + k / 12):.2g}") for k in range(73)],      # 1e-7 .. 1e-1
              "hmc": [float(f"{10.0 ** (-4 + k / 12):.2g}") for k in range(43)]}       # 1e-4 .. 0.3
     for case in sys.argv[1:] or list(CASES):

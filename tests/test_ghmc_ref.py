@@ -153,6 +153,7 @@ def test_the_cases_tables_are_what_measure_computes_and_no_decision_is_borderlin
     print(f"{case} mass {mass}: accepted {acc.sum(1)}, of {acc.shape[1]}; smallest | log|s| + dH | {m.min():.3g} (dH tolerance {tol[3]:.3g})")
     assert m.min() > 10 * tol[3]                                       # no |s| within the tolerance of exp(-dH)
     assert acc.sum() >= 2 and (~acc).sum() >= 2                        # both decisions occur
+    assert gc.alpha_one_both(case, mass) >= 2                          # the alpha = 1 comparison with HMC has chains to compare
     for _, (s64, i64), (s32, i32) in gc.walk(case, mass):
         np.testing.assert_array_equal(i64.is_accepted, i32.is_accepted)
 

@@ -3,7 +3,7 @@ warmup.hip, ``mfm_hmc_warmup_window``) and of the window adaptation built on the
 
 * ONES ARE FREE: with a vector of ones installed every HMC entry point gives the bits it gives with none installed (the mass
   instances against the unit instances), one shape per instance family: the mixture d = 2, phi-four d = 64 / 256 / 272 / 1040
-  (MAXIT 1 / 4 / 16 / 32) and the periodic chain at d = 64 (the run-time boundary); ``mfm_hmc_warmup_window`` with none installed equals
+  (MAXIT 1 / 4 / 16 / 32) and the periodic chain at d = 64 and d = 272 (the run-time boundary at MAXIT 1 and 16);``mfm_hmc_warmup_window`` with none installed equals
   ``mfm_hmc_warmup``.  Chain counts are 16 and 32: ``mfm_create`` takes multiples of 16 only, so a chain count that is not a multiple of
   the four chains of a workgroup cannot be built.
 * THE STEP against the float64 restatement (tests/hmc_mass_ref.py, pinned to oracle/hmc.py by tests/test_hmc_mass_host.py) with
@@ -14,7 +14,7 @@ warmup.hip, ``mfm_hmc_warmup_window``) and of the window adaptation built on the
   keys just below the stability limit of velocity Verlet under this ``minv`` (0.6 to 0.65 of the unit-mass sizes of
   tests/test_gpu_hmc_run.py), so that accepted and rejected steps both occur -- restatement, accepted steps of a 6-step run on the
   step-major / chain-major keys: d = 64 at 0.0572: 167 / 166 of 192, periodic at 0.0572: 87 / 86 of 96, d = 256 at 0.0267: 21 / 21,
-  d = 272 at 0.0259: 49 / 56, d = 1040 at 0.0133: 16 / 16, the mixture at 0.9: 60 of 96.  From these starts every chain's acceptance
+  d = 272 at 0.0259: 49 / 56 (Dirichlet and periodic alike), d = 1040 at 0.0133: 16 / 16, the mixture at 0.9: 60 of 96.  From these starts every chain's acceptance
   probability is exactly 0 or 1 at first, so the chains' step sizes part late: the windows run 8 steps where the restatement parts
   by the 8th (mixture: 2nd step; d = 64, also periodic: 8th) and 14 steps above d = 64 (d = 256 and 272: 12th; d = 1040: 13th).
 * The errors, the adaptation end to end against the restated driver, ``--adapt_mass``."""
@@ -22,7 +22,7 @@ import numpy as np
 import pytest
 
 from oracle import mala as omala, prng, targets
-from tests import hmc_mass_ref as mr, warmup_ref as wr
+from tests import hmc_mass_ref as mr, row_instance_cases as rc, warmup_ref as wr
 from tests.test_gpu_hmc_run import L, _assert_run_equals_steps, _ctx, _init, _keys_dev, _run, _stepwise
 
 pytestmark = pytest.mark.gpu
@@ -37,6 +37,7 @@ FAMILIES = {
     "phi4_d272": ("phi4", 272, None, 16, 0.0432, 0.0259, 14),
     "phi4_d1040": ("phi4", 1040, None, 16, 0.0221, 0.0133, 14),
     "phi4_d64_pbc": ("phi4", 64, [1.0, 0.0], 16, 0.088, 0.0572, 8),
+    "phi4_d272_pbc": ("phi4", 272, [1.0, 0.0], 16, 0.0432, 0.0259, 14),        # the run-time boundary on a MAXIT 16 mass instance
 }
 
 
@@ -111,7 +112,10 @@ BOTH_DECISIONS = {"gmm4", "gmm16", "phi4-64-large", "phi4-48-large"}
 LARGE_EPS = {"phi4-64-large": 0.065, "phi4-48-large": 0.07}
 
 
-@pytest.mark.parametrize("case", ["phi4-64", "phi4-256", "phi4-48", "gmm4", "gmm16", "phi4-64-large", "phi4-48-large"])
+STEP_CASES = ["phi4-64", "phi4-256", "phi4-48", "gmm4", "gmm16", "phi4-64-large", "phi4-48-large"]
+
+
+@pytest.mark.parametrize("case", STEP_CASES)
 def test_mass_step_matches_the_float64_restatement(case):
     """tests/test_gpu_hmc.py::test_hmc_step_matches_oracle with ``minv`` log-spaced over [0.25, 4]: same cases, step sizes, protocol
     (both sides continue from the kernel's decisions, borderline decisions excluded) and tolerances."""
@@ -161,6 +165,65 @@ def test_mass_step_matches_the_float64_restatement(case):
         st = omala.MALAState(pos.cpu().numpy().astype(np.float64), logp.cpu().numpy(), grad.cpu().numpy().astype(np.float64))
     assert True in seen, case                                   # chains move
     assert False in seen or case not in BOTH_DECISIONS, case    # at least one proposal rejected (see BOTH_DECISIONS)
+    ctx.close()
+
+
+@pytest.mark.parametrize("variant", list(rc.VARIANTS))
+@pytest.mark.parametrize("case", rc.MASS_CASES)
+def test_mass_step_matches_the_float64_restatement_above_d_256(case, variant):
+    """``hmc_trajectory<MAXIT 16 / 32, BCRT false / true, MASS>`` (and BCRT at MAXIT 4: d65_pbc) against tests/hmc_mass_ref.py, element by element: the protocol of
+    tests/test_gpu_row_instances.py::test_hmc_step_and_step_keys_match_oracle (16 chains from ``rc.start_state``, 3 steps of 3 leapfrog
+    steps, both sides continue from the kernel's decisions, the seam set asserted on its own) with ``minv = rc.inverse_mass(case)``
+    installed -- log-spaced over [0.25, 4] in a fixed permutation, so a ``minv`` read at another element moves x by up to 16 x eps p.
+    Tolerances: that test's, with ``rc.HMC_MASS_F32_DISTANCE`` (the restatement against its device-format variant under this mass, on
+    the CPU) where it has ``HMC_F32_DISTANCE``.  tests/test_row_instance_cases.py asserts on the restatement alone that both decisions
+    occur and at most 1 of 16 chains per step lies in the band.
+    Measured on MI355X, largest error / tolerance over both variants (log acceptance probability, position, log-density, gradient):
+    d65_pbc 0.24 0.040 0.14 0.013; d257_d0 0.084 0.047 0.11 0.060; 17x17_db 0.021 0.045 0.023 0.0090; d1025_d0 0.12 0.047 0.27 0.25;
+    d2048_pbc 0.20 0.057 0.30 0.59."""
+    import torch
+    from tests.test_gpu_row_instances import B, _ctx as _row_ctx, _merge, _report, _rows, _state, _vec
+    beta = rc.VARIANTS[variant][0]
+    eps = rc.MASS_STEP_SIZES[case][variant]
+    minv = rc.inverse_mass(case)
+    ctx, pos = _row_ctx(case)
+    ctx.set_inverse_mass(minv)
+    vg = rc.value_and_grad(case, variant)
+    logp, grad = _state(ctx, pos, beta)
+    info = lambda: (torch.empty(B, device="cuda"), torch.empty(B, dtype=torch.uint8, device="cuda"))
+    seen, worst = set(), {}
+    for j in range(rc.N_STEPS):
+        key, keys = rc.step_keys(case, j, "hmc_mass")
+        x0, lp0, g0 = pos.cpu().numpy().astype(np.float64), logp.cpu().numpy(), grad.cpu().numpy().astype(np.float64)
+        st = omala.MALAState(x0, lp0, g0)
+        new, o, u = rc.oracle_step("hmc_mass", variant, st, vg, keys, eps)
+        by_keys = (pos.clone(), logp.clone(), grad.clone()) + info()
+        ctx.hmc_step_keys(_keys_dev(keys), beta, eps, rc.HMC_LEAPFROG, *by_keys)
+        acc, isacc = info()
+        ctx.hmc_step(key, beta, eps, rc.HMC_LEAPFROG, pos, logp, grad, acc, isacc)
+        for name, a, b in zip(("pos", "logp", "grad", "acc", "isacc"), (pos, logp, grad, acc, isacc), by_keys):
+            np.testing.assert_array_equal(a.cpu().numpy(), b.cpu().numpy(), err_msg=f"step {j}: hmc_step vs hmc_step_keys, {name}")
+        ia_g, pa_g = isacc.cpu().numpy().astype(bool), acc.cpu().numpy().astype(np.float64)
+        tol = 5e-6 * max(1.0, np.abs(lp0).max())
+        f32_p, f32_lp = (4 * v for v in rc.HMC_MASS_F32_DISTANCE[case][variant])
+        _merge(worst, scale=np.abs(lp0).max(),
+               p=_vec(f"step {j} log acceptance probability", np.log(np.maximum(pa_g, 1e-30)), np.log(np.maximum(o.acceptance_rate, 1e-30)), 0.0,
+                      max(tol + 1e-5, f32_p)))
+        border = rc.borderline("hmc_mass", st, o, u)
+        assert border.sum() <= 1, (j, int(border.sum()))
+        np.testing.assert_array_equal(ia_g[~border], o.is_accepted[~border], err_msg=f"step {j} decisions")
+        seen |= set(ia_g.tolist())
+        lpn, gn = vg(o.proposed_position)
+        m = ia_g[:, None]
+        ref_x, ref_lp, ref_g = np.where(m, o.proposed_position, x0), np.where(ia_g, lpn, lp0), np.where(m, gn, g0)
+        np.testing.assert_array_equal(pos.cpu().numpy()[~ia_g], x0[~ia_g].astype(np.float32))
+        np.testing.assert_array_equal(logp.cpu().numpy()[~ia_g], lp0[~ia_g])
+        np.testing.assert_array_equal(grad.cpu().numpy()[~ia_g], g0[~ia_g].astype(np.float32))
+        _merge(worst, x=_rows(f"step {j} position", case, pos.cpu().numpy(), ref_x, 0.0, 3e-6 * max(1.0, np.abs(ref_x).max())),
+               logp=_vec(f"step {j} log-density", logp.cpu().numpy(), ref_lp, 0.0, max(2e-6 * max(1.0, np.abs(ref_lp).max()), f32_lp)),
+               grad=_rows(f"step {j} gradient", case, grad.cpu().numpy(), ref_g, 3e-5, 3e-3))
+    assert seen == {True, False}, seen
+    _report(case, f"hmc_mass/{variant}", worst)
     ctx.close()
 
 

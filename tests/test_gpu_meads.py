@@ -140,6 +140,10 @@ def _check_against_the_restatement(case, before, trace, mass, res, minv_out):
 
 @pytest.mark.parametrize("case", mc.CASES)
 def test_warmup_replays_bit_for_bit_and_matches_the_restatement(case):
+    """Measured on MI355X, worst relative error of lam(Z) / lam(Y) over iterations and folds (tolerances in tests/meads_cases.py):
+    d320_k4 4.2e-7 / 2.6e-7; d1100_k4 9.8e-7 / 3.4e-7; d64_pbc_k4 1.5e-7 / 7.4e-8; d65_pbc_k4 1.3e-7 / 8.3e-8; 32x32_k4 4.4e-7 / 3.5e-7;
+    d1025_pbc_k4 6.1e-7 / 2.6e-7; k6 1.9e-7 / 9.1e-8 -- 1e-4 to 5e-3 of the tolerances, which carry the worst-case float32 dot-product
+    bound; inverse mass within 1e-12 and the replay bit for bit in every case."""
     B, n_valid, K, S, n_iter, step0, alpha0 = mc.shape(case)
     ctx = _ctx(case)
     state0 = _start(ctx, case)

@@ -124,7 +124,9 @@ def test_warmup_uses_the_previous_folds_statistics_and_the_run_keys():
 def test_the_cases_table_no_borderline_decision_and_no_parameter_at_its_clamp(case):
     tol = mc.tolerance(case)
     assert tol == mc.TOLERANCE[case], (case, tol)
-    assert all(0 < v < 1e-3 for v in tol)
+    # the formats cost something, and little; the eigenvalue tolerances carry the dot-product bound (d + 8) 2^-23 per Gram entry, which
+    # at d = 1100 is 15 x what it is at d = 65, so above d = 320 they are held to 1e-2
+    assert all(0 < v < 1e-3 for v in tol) or (mc.dim(case) > 320 and all(0 < v < 1e-2 for v in tol[:2]) and 0 < tol[2] < 1e-3)
     res = mc.reference(case)
     B, n_valid, K, S, n_iter, step0, alpha0 = mc.shape(case)
     m, acc = mc.decision_margins(case)
@@ -158,4 +160,9 @@ def test_the_cases_reach_what_they_are_meant_to():
     assert sh.shape == (2, 16)
     B, n_valid = mc.shape("n_valid")[:2]
     assert n_valid < B
+    B, n_valid, K = mc.shape("k6")[:3]
+    assert K > 4 and n_valid // K >= 2                                            # a wave of the update kernel owns two folds
+    from tests import row_instance_cases as rc
+    assert {rc.maxit(mc.dim(c)) for c in mc.CASES} == {1, 4, 16, 32} and max(mc.dim(c) for c in mc.CASES) > 1024
+    assert all(np.isfinite(mc.reference(c).trace[:, :, :5]).all() for c in mc.NEW_CASES)      # their statistics are all usable
     assert mc.reference("n_valid").trace.shape == (3, 4, 6)

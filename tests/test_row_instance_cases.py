@@ -33,6 +33,49 @@ def test_both_decisions_occur_and_the_band_excludes_at_most_one_chain(case, samp
         assert (ratio <= 1.0).sum() <= 1, (case, sampler, variant, j, int((ratio <= 1.0).sum()))
 
 
+def test_the_mass_cases_cover_the_cells_above_d_256_and_the_boundary_at_maxit_4():
+    cells = {(rc.maxit(rc.CASES[c][0]), rc.bcrt(c)) for c in rc.MASS_CASES}
+    assert cells == {(4, True), (16, False), (16, True), (32, False), (32, True)}
+    assert any(rc.CASES[c][1] and rc.CASES[c][2] == "db" for c in rc.MASS_CASES)           # a lattice with a held frame among them
+    assert set(rc.MASS_STEP_SIZES) == set(rc.HMC_MASS_F32_DISTANCE) == set(rc.MASS_CASES)
+    for c in rc.MASS_CASES:
+        m = rc.inverse_mass(c)
+        assert m.shape == (rc.CASES[c][0],) and m.min() == 0.25 and abs(m.max() - 4.0) < 1e-12
+
+
+@pytest.mark.parametrize("variant", list(rc.VARIANTS))
+@pytest.mark.parametrize("case", rc.MASS_CASES)
+def test_mass_both_decisions_occur_and_the_band_excludes_at_most_one_chain(case, variant):
+    """The conditions of the unit-mass cases, for the step under ``inverse_mass(case)``; and none of the chains sits near the band's
+    edge (within a quarter of its width), as ``scan`` chose."""
+    res = rc.oracle_run(case, "hmc_mass", variant)
+    acc = np.stack([r[0] for r in res])
+    assert 0 < acc.sum() < acc.size, (case, variant, int(acc.sum()))
+    for j, (_, ratio, _) in enumerate(res):
+        assert (ratio <= 1.0).sum() <= 1, (case, variant, j, int((ratio <= 1.0).sum()))
+        assert not ((ratio > 0.75) & (ratio < 1.25)).any(), (case, variant, j)
+
+
+@pytest.mark.parametrize("case", rc.MASS_CASES)
+def test_the_mass_float32_distance_table_is_the_restatement_against_the_oracle(case):
+    for variant in rc.VARIANTS:
+        for got, kept in zip(rc.hmc_f32_distance(case, variant, "hmc_mass"), rc.HMC_MASS_F32_DISTANCE[case][variant]):
+            assert got <= kept <= 1.11 * got, (case, variant, got, kept)
+        # outside the band the device-format restatement makes the float64 restatement's decisions
+        from oracle import mala as omala
+        vg = rc.value_and_grad(case, variant)
+        st = omala.init(rc.start_state(case).astype(np.float64), vg)
+        for j in range(rc.N_STEPS):
+            keys = rc.step_keys(case, j, "hmc_mass")[1]
+            new, info, u = rc.oracle_step("hmc_mass", variant, st, vg, keys, rc.MASS_STEP_SIZES[case][variant])
+            lpa = rc.hmc_step_f32(case, variant, st, keys, rc.MASS_STEP_SIZES[case][variant], rc.inverse_mass(case))[0]
+            out = ~rc.borderline("hmc_mass", st, info, u)
+            np.testing.assert_array_equal((u < np.exp(lpa))[out], info.is_accepted[out])
+            st = omala.init(new.position.astype(np.float32).astype(np.float64), vg)
+    grid = [float(f"{10.0 ** (-4 + k / 12):.2g}") for k in range(43)]
+    assert rc.scan(case, "hmc_mass", "b1", grid) == rc.MASS_STEP_SIZES[case]["b1"]
+
+
 def test_start_states_are_near_a_mode():
     """|log pi| of the start states at beta = 1: the scale the tolerances of the device test are relative to."""
     from oracle import mala
